@@ -7,7 +7,7 @@ on 50 M synthetic 150 bp Phred+33 reads PER GPU (seed 2, SURVEY.md 8d generator,
 device so inputs are resident in HBM when the timed region starts), fused into ONE pass that also
 stream-compacts the kept, trimmed reads in input order.  One "step" = one such pass over the batch.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--reads R] [--config cfg2|cfg3|cfg4|cfg5shard|stats]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--reads R] [--config cfg2|cfg3|cfg4|cfg5shard|stats] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
            bench.py --gpus N --steps K --warmup W
 
@@ -16,6 +16,10 @@ stream-compacts the kept, trimmed reads in input order.  One "step" = one such p
     cfg4       fastx_reverse_complement | fastx_trimmer -f 5 -l 145 fused, 200 M x 150 bp
     cfg5shard  clip -> quality-trim -> filter in one pass, 125 M x 150 bp per GPU (1 B reads over 8 GPUs)
     stats      fastx_quality_stats histogram reduction, 50 M x 150 bp
+
+--dump-outputs DIR writes what the timed path computed in its last step as DIR/<name>.npy (float64 / float32, under 64 MB): the counter
+block, res[] and the packed bases and qualities at fixed seeded sample positions, and the stream checksum over all of them (statistics:
+the histogram one step added).  The inputs are seeded, so two builds run with the same arguments can be compared output for output.
 
 Multi-GPU: reads shard by contiguous index range (rank g owns reads [g*R, (g+1)*R) of the global set),
 no data-path collective; each step ends with one 192-byte all-gather of the counter blocks (RCCL) from
@@ -90,6 +94,47 @@ def csrc_sha16():
     for f in sorted(os.listdir(d)):
         h.update(f.encode()); h.update(open(os.path.join(d, f), "rb").read())
     return h.hexdigest()[:16]
+
+
+DUMP_SEED = 20251015
+DUMP_RES = 1 << 21          # sampled res[] entries (float64: 16 MB)
+DUMP_STREAM = 1 << 22       # sampled bytes of each packed stream (float32: 16 MB each)
+DUMP_COUNTERS = 17          # counter slots FXG_C_INPUT .. FXG_C_ARTIFACT_DROPPED (include/fxg.h); the rest are not results
+
+
+def _sample(t, n, count, salt):
+    """t[i] for a fixed, seeded, sorted set of `count` positions in [0, n) (all of them when n <= count), on the host."""
+    import numpy as np
+    import torch
+    if n <= count:
+        return t[:n].cpu().numpy()
+    idx = np.unique(np.random.default_rng([DUMP_SEED, salt]).integers(0, n, size=count, dtype=np.int64))
+    return t.index_select(0, torch.from_numpy(idx).to(t.device)).cpu().numpy()
+
+
+def dump_outputs(d, suffix, res=None, hist=None, per_step=1):
+    """The arrays a caller of the timed path receives from its last step, as DIR/<name><suffix>.npy."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    out = {}
+    if hist is not None:                             # quality_stats accumulates: every step added the same counts
+        h = hist.cpu().numpy()
+        assert not (h % per_step).any()
+        out["hist"] = (h // per_step).astype(np.float64)
+    else:
+        c = np.asarray(res.counters[:DUMP_COUNTERS], dtype=np.uint64)
+        out["counters"] = c.astype(np.float64)
+        out["res_sample"] = _sample(res.res, res.res.numel(), DUMP_RES, 1).view(np.uint32).astype(np.float64)
+        if res.out_bases is not None:
+            nbytes = res.kept_bytes
+            out["out_bases_sample"] = _sample(res.out_bases, nbytes, DUMP_STREAM, 2).astype(np.float32)
+            if res.out_qual is not None:
+                out["out_qual_sample"] = _sample(res.out_qual, nbytes, DUMP_STREAM, 3).astype(np.float32)
+            cs = res.checksum()                      # the whole of res[] and both streams, 63 bits as two exact 32-bit halves
+            out["checksum_hi_lo"] = np.array([cs >> 32, cs & 0xFFFFFFFF], dtype=np.float64)
+    for k, a in out.items():
+        np.save(os.path.join(d, k + suffix + ".npy"), a)
+    return sorted(out)
 
 
 def physical_cores():
@@ -546,6 +591,7 @@ def main():
     ap.add_argument("--e2e-reads", type=int, default=32_000_000, help="reads per rank of the --e2e leg")
     ap.add_argument("--decision-only", action="store_true", help="no compaction: 154 B/read variant (not the headline)")
     ap.add_argument("--headline-only", action="store_true", help="the default config alone, without the other BASELINE configs behind it")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed step's outputs of the measured config as DIR/<name>.npy")
     args = ap.parse_args()
     if args.steps < 1:
         raise SystemExit("--steps must be at least 1")
@@ -566,7 +612,7 @@ def main():
     torch.cuda.set_stream(torch.cuda.Stream(device=local))
     eng = Engine(local)
 
-    def measure(config, steps, warmup, reads, want_e2e):
+    def measure(config, steps, warmup, reads, want_e2e, dump=None):
         cfg = CONFIGS[config]
         R, L = (reads or cfg["reads"]), cfg["L"]
         lo = rank * R                                  # weak scaling: rank g owns reads [g*R, (g+1)*R) of the global set
@@ -612,6 +658,10 @@ def main():
         dt = time.perf_counter() - t0
         kms = eng.profiled_kernel_ms(min(steps, 64))
         eng.set_profiling(False)
+        dumped = None
+        if dump:                                       # after the timed region: sampling and the checksum are not timed
+            dumped = dump_outputs(dump, "" if world == 1 else "_rank%d" % rank, res=None if is_stats else res,
+                                  hist=hist if is_stats else None, per_step=warmup + steps)
         if world > 1:
             t = torch.tensor([dt], dtype=torch.float64, device=eng.device if dist.get_backend() == "nccl" else "cpu")
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -758,10 +808,12 @@ def main():
                 out["self_check"] = self_check
             if e2e_r is not None:
                 out["e2e_ranks"] = e2e_r
+            if dumped is not None:
+                out["dumped_outputs"] = dict(dir=os.path.abspath(dump), arrays=dumped)
             return out
         return None
 
-    out = measure(args.config, args.steps, args.warmup, args.reads, args.e2e)
+    out = measure(args.config, args.steps, args.warmup, args.reads, args.e2e, dump=args.dump_outputs)
     if rank == 0:
         if world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(args.config)

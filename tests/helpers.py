@@ -1,13 +1,32 @@
 """Shared helpers for the parity tests (oracle side = checker only)."""
 import hashlib
 import os
+import subprocess
 
 import numpy as np
 
+import fxref_replay
 from oracle import fxoracle_py as fo
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 KEYS = ("res", "out_bases", "out_qual", "out_len", "kept_index")
+REPLAY = fxref_replay.__file__
+
+
+def ref_driver():
+    """The reference driver the tests compare with: oracle/_ref/fxref where it was built (that needs the reference's sources), otherwise
+    the recorded answers of tests/fxref_replay.py (which, under FXREF_RECORD, records them).  run_ref() runs either."""
+    if os.environ.get("FXREF_RECORD"):
+        return REPLAY
+    return fo.ref_binary() or REPLAY
+
+
+def run_ref(cmd, data=b"", timeout=None):
+    """cmd = [ref_driver()] + argv, data on stdin -> (exit code, stdout, stderr)."""
+    if cmd[0] == REPLAY:
+        return fxref_replay.answer(list(cmd[1:]), data)
+    p = subprocess.run(cmd, input=data, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=timeout)
+    return p.returncode, p.stdout, p.stderr
 
 
 def md5(b):

@@ -2,7 +2,7 @@
 
 * every Galaxy known-answer pair of the hot tools, byte for byte;
 * the seeded synthetic cases of tests/golden/cases.json by md5 (reference output);
-* where oracle/_ref/fxref travelled to the box: fuzzed text incl. -v reports, exit codes and the
+* against the reference driver (oracle/_ref/fxref, or its recorded answers: tests/fxref_replay.py): fuzzed text incl. -v reports, exit codes and the
   "flush everything before the bad record, then fail with the reference's message" behaviour.
 """
 import os
@@ -12,12 +12,12 @@ import numpy as np
 import pytest
 
 from conftest import ROOT
-from helpers import GOLDEN, md5
+from helpers import GOLDEN, md5, ref_driver, run_ref
 from oracle import fxoracle_py as fo
 
 pytestmark = pytest.mark.gpu
 HOST = os.path.join(ROOT, "fastx_toolkit_amd", "host")
-REF = fo.ref_binary()
+REF = ref_driver()
 
 
 @pytest.fixture(scope="module")
@@ -30,6 +30,8 @@ PARSE_ENV = {}          # set per test run by the `parse_mode` fixture: {} = dev
 
 
 def _run(cmd, data, env=None):
+    if cmd[0] == REF:
+        return run_ref(cmd, data)
     env = dict(env or os.environ, **PARSE_ENV)
     p = subprocess.run(cmd, input=data, stdout=subprocess.PIPE, stderr=subprocess.PIPE, env=env, timeout=180)   # a hang must fail fast
     return p.returncode, p.stdout, p.stderr

@@ -5,7 +5,7 @@ import os
 import numpy as np
 import pytest
 
-from helpers import GOLDEN, md5, oracle_params, text_through
+from helpers import GOLDEN, md5, oracle_params, ref_driver, run_ref, text_through
 from oracle import fxoracle_py as fo
 
 pytestmark = pytest.mark.gpu
@@ -118,13 +118,12 @@ def test_irregular_input_is_detected_not_processed(engine):
 
 
 def _ref(argv, data):
-    import subprocess
-    p = subprocess.run([fo.ref_binary()] + argv, input=data, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=120)
-    assert p.returncode == 0, p.stderr
-    return p.stdout
+    rc, out, err = run_ref([ref_driver()] + argv, data, timeout=120)
+    assert rc == 0, err
+    return out
 
 
-@pytest.mark.skipif(fo.ref_binary() is None, reason="oracle/_ref/fxref not on this box")
+@pytest.mark.skipif(ref_driver() is None, reason="oracle/_ref/fxref not on this box")
 def test_crlf_numeric_and_fasta_on_the_device_vs_reference(engine):
     """R2 (chomp at the first CR or LF), R6 (numeric quality lines, per record; output in the record's own encoding) and FASTA
     (two-line records, collapsed ids) go through the device text path; expected output = the real libfastx around the same stage."""
@@ -163,8 +162,6 @@ def test_crlf_numeric_and_fasta_on_the_device_vs_reference(engine):
             out, info, _ = _gpu_text_pipeline(engine, text, pd, fasta=True)
             assert out == _ref(argv, text), (name, argv)
     # collapsed identifiers: the -v tallies count reads, not records
-    import subprocess
-    p = subprocess.run([fo.ref_binary(), "fastx_artifacts_filter", "-v"], input=fa, stdout=subprocess.PIPE, stderr=subprocess.PIPE)
-    rep = p.stderr.decode()
+    rep = run_ref([ref_driver(), "fastx_artifacts_filter", "-v"], fa)[2].decode()
     out, info, _ = _gpu_text_pipeline(engine, fa, dict(stages=128), fasta=True)
     assert "Input: %d reads." % info.weights[0] in rep and "Output: %d reads." % info.weights[1] in rep

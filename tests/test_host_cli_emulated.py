@@ -14,12 +14,12 @@ import numpy as np
 import pytest
 
 from conftest import ROOT
-from helpers import GOLDEN, md5
+from helpers import GOLDEN, md5, ref_driver, run_ref
 from oracle import fxoracle_py as fo
 
 HOST = os.path.join(ROOT, "fastx_toolkit_amd", "host")
 STUB_DIR = os.path.join(ROOT, "tests", "emu", "stub")
-REF = fo.ref_binary()
+REF = ref_driver()
 
 
 @pytest.fixture(scope="module")
@@ -33,6 +33,8 @@ def tools():
 
 
 def _run(cmd, data, threads="4", buf_mb=None, extra_env=None):
+    if cmd[0] == REF:
+        return run_ref(cmd, data)
     env = dict(os.environ, LD_LIBRARY_PATH=STUB_DIR, FXH_THREADS=threads)
     if buf_mb:
         env["FXH_READ_BUFFER_MB"] = buf_mb

@@ -2,8 +2,8 @@
 against the reference's reader/writer, through the GPU-free demo tool host/bin/fastx_copy.
 
 Reference side: `fxref fastx_trimmer -f 1` is the identity transform around the reference's own
-fastx_read_next_record + fastx_write_record (skipped where oracle/_ref is absent; the Galaxy inputs are
-then still checked for round-tripping).
+fastx_read_next_record + fastx_write_record (where oracle/_ref is absent, the driver's recorded answers:
+tests/fxref_replay.py).
 """
 import os
 import subprocess
@@ -12,11 +12,11 @@ import numpy as np
 import pytest
 
 from conftest import ROOT
-from helpers import GOLDEN
+from helpers import GOLDEN, ref_driver, run_ref
 from oracle import fxoracle_py as fo
 
 HOSTBIN = os.path.join(ROOT, "fastx_toolkit_amd", "host", "bin")
-REF = fo.ref_binary()
+REF = ref_driver()
 
 
 @pytest.fixture(scope="module")
@@ -26,6 +26,8 @@ def copy_tool():
 
 
 def _run(cmd, data):
+    if cmd[0] == REF:
+        return run_ref(cmd, data)
     p = subprocess.run(cmd, input=data, stdout=subprocess.PIPE, stderr=subprocess.PIPE)
     return p.returncode, p.stdout, p.stderr
 

@@ -1,25 +1,23 @@
 """CPU tier: the C restatement against the REAL reference libfastx (oracle/_ref/fxref) on fuzzed FASTQ text.
 
-Skipped where oracle/_ref was never built (it needs /root/reference); the md5 fixtures in
-test_oracle_golden.py carry the same evidence to machines without it.
+Where oracle/_ref was never built (it needs the reference's sources) the real driver's recorded answers stand in for it
+(tests/fxref_replay.py, tests/golden/fxref_answers.xz).
 """
-import subprocess
 
 import numpy as np
 import pytest
 
-from helpers import oracle_params, text_through
+from helpers import oracle_params, ref_driver, run_ref, text_through
 from oracle import fxoracle_py as fo
 
-REF = fo.ref_binary()
+REF = ref_driver()
 pytestmark = pytest.mark.skipif(REF is None, reason="oracle/_ref/fxref not built")
 
 
 def _ref(text, chain):
     for cmd in chain:
-        p = subprocess.run([REF] + cmd, input=text, stdout=subprocess.PIPE, stderr=subprocess.PIPE)
-        assert p.returncode == 0, p.stderr
-        text = p.stdout
+        rc, text, err = run_ref([REF] + cmd, text)
+        assert rc == 0, err
     return text
 
 
@@ -115,7 +113,7 @@ def test_aligner_fields_vs_reference():
     for _ in range(40):
         q = rng.choice(np.frombuffer(b"ACGTN", np.uint8), size=int(rng.integers(1, 60))).tobytes()
         t = rng.choice(np.frombuffer(b"ACGTN", np.uint8), size=int(rng.integers(1, 30))).tobytes()
-        out = subprocess.run([REF, "align", q.decode(), t.decode()], stdout=subprocess.PIPE).stdout.split()
+        out = run_ref([REF, "align", q.decode(), t.decode()])[1].split()
         r = fo.align(q, t)
         assert [int(x) for x in out] == [r.query_start, r.query_end, r.target_start, r.target_end, r.matches, r.mismatches,
                                          r.neutral_matches, r.gaps]
