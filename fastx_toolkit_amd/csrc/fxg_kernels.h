@@ -716,12 +716,17 @@ FXG_HD int fxg_clip_two_pass(const FxgKArgs &a, const uint8_t *rd, int len, int 
         // The best path covers at most SPAN rows (above), i.e. starts in row rs = bq1 - SPAN + 1 or later: rows r0 .. rs - 1 re-run the SCORES only
         // (the cheap row of pass 1), rows rs .. bq1 carry the summaries, whose start field counts from rs.  Every lane is at rows of its own
         // here; the fetch pipeline is the one of pass 1 (values of row q in registers, table offset of row q + 1, base of row q + 2).
+        // GL: the look-ahead bases of rows past bq1 are fetched but never scored; they are read at the row's last byte instead (rows - 1 >= bq1):
+        // row bq1 may be the array's last byte (the batch's last read at len == stride), and q + 3 would run up to two bytes past it.  (The
+        // staged form reads its tile in LDS, where a look-ahead past the tile cannot fault; it keeps the unclamped index.)
         constexpr int SPAN = FxgClip2<AMAX>::SPAN;
         const int rs = bq1 - SPAN + 1 > r0 ? bq1 - SPAN + 1 : r0;
         const uint16_t *lut = reinterpret_cast<const uint16_t *>(ptab);
+        const int qlast = rows - 1;
+#define FXG_RD_AHEAD(i) rd[GL && (i) > qlast ? qlast : (i)]
         {
             const u32 o0 = lut[rd[q]];
-            on = lut[rd[q + 1]]; cn = rd[q + 2];
+            on = lut[FXG_RD_AHEAD(q + 1)]; cn = FXG_RD_AHEAD(q + 2);
             fxg_ptab_fetch<AMAX, true>(ptab, o0, step_off, pr, st);
         }
         const int n0 = rs - r0, n0u = fxg_wave_max(n0);
@@ -729,7 +734,7 @@ FXG_HD int fxg_clip_two_pass(const FxgKArgs &a, const uint8_t *rd, int len, int 
         for (int i = 0; i < n0u; ++i) {
             if (i >= n0) continue;
             const u32 on2 = lut[cn];
-            cn = rd[q + 3];
+            cn = FXG_RD_AHEAD(q + 3);
             (void)fxg_clip_row_score_t<AMAX, true, true>(A, q, S, Sm, pr, st, ptab, on, step_off);      // (the early form tests the row number itself)
             on = on2; ++q;
         }
@@ -742,7 +747,7 @@ FXG_HD int fxg_clip_two_pass(const FxgKArgs &a, const uint8_t *rd, int len, int 
         for (int i = 0; i < n1u; ++i) {
             if (i >= n1) continue;
             const u32 on2 = lut[cn];
-            cn = rd[q + 3];
+            cn = FXG_RD_AHEAD(q + 3);
             fxg_clip_row_packed_t<AMAX, true, false>(A, q, (u32)(q - rs), S, Sm, W, best, bw, bq, pr, st, ptab, on, step_off);
             on = on2; ++q;
         }
@@ -750,11 +755,12 @@ FXG_HD int fxg_clip_two_pass(const FxgKArgs &a, const uint8_t *rd, int len, int 
         for (int i = 0; i < n2u; ++i) {
             if (i >= n2) continue;
             const u32 on2 = lut[cn];
-            cn = rd[q + 3];
+            cn = FXG_RD_AHEAD(q + 3);
             fxg_clip_row_packed_t<AMAX, false, false>(A, q, (u32)(q - rs), S, Sm, W, best, bw, bq, pr, st, ptab, on, step_off);
             on = on2; ++q;
         }
         fxg_clip_row_packed_t<AMAX, true, true>(A, bq1, (u32)(bq1 - rs), S, Sm, W, best, bw, bq, pr, st, ptab, on, step_off);
+#undef FXG_RD_AHEAD
 #if defined(FXG_ABL_ROWCLK) && !defined(FXG_HOST_EMULATION)
         if ((threadIdx.x & 63u) == 0u) { atomicAdd(reinterpret_cast<u64 *>(a.errflag + 10) + 2, __builtin_amdgcn_s_memtime() - clk_b); atomicAdd(reinterpret_cast<u64 *>(a.errflag + 10) + 3, (u64)(n0u + n1u + n2u + 1)); atomicAdd(reinterpret_cast<u64 *>(a.errflag + 10) + 4, (u64)n0u); }
 #endif

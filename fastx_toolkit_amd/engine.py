@@ -363,8 +363,8 @@ class Engine:
     def alloc_outputs(self, n, stride, compact=True, meta=True, has_qual=True):
         t = self.torch
         o = dict(res=t.empty(n, dtype=t.int32, device=self.device), counters=t.zeros(NCOUNTERS, dtype=t.int64, device=self.device))
-        o["out_bases"] = t.empty(n * stride + 16, dtype=t.uint8, device=self.device) if compact else None
-        o["out_qual"] = t.empty(n * stride + 16, dtype=t.uint8, device=self.device) if (compact and has_qual) else None
+        o["out_bases"] = t.empty(n * stride, dtype=t.uint8, device=self.device) if compact else None      # the contracted capacity (include/fxg.h)
+        o["out_qual"] = t.empty(n * stride, dtype=t.uint8, device=self.device) if (compact and has_qual) else None
         o["out_len"] = t.empty(n, dtype=t.int16, device=self.device) if (compact and meta) else None
         o["kept_index"] = t.empty(n, dtype=t.int32, device=self.device) if (compact and meta) else None
         o["out_off"] = t.empty(n, dtype=t.int64, device=self.device) if (compact and meta) else None

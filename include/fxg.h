@@ -166,6 +166,22 @@ typedef struct fxg_out {
     uint64_t *counters;
 } fxg_out;
 
+/* Memory contract: the bytes a kernel may touch through each pointer, counted from the pointer.  "Granule": the 16-byte aligned block that holds
+ * an array's last byte.  An input may be read up to the end of that granule (aligned 16-byte loads; a granule never crosses a page), and what is
+ * read there never reaches a result.  Nothing before a pointer is read, and nothing outside an output's range is written.
+ *   fxg_batch.bases, .qual   read   n * stride bytes (+ granule)      every row whole, also past len[r]; qual may be NULL
+ *   fxg_batch.len            read   n uint16 (+ granule)               NULL: every read is fixed_len long
+ *   fxg_out.res              write  n uint32
+ *   fxg_out.out_bases, .out_qual   write  n * stride bytes            the capacity; the kept reads fill counters[FXG_C_KEPT_BASES] <= n * stride of it
+ *   fxg_out.out_len          write  n uint16      kept_index: n uint32      out_off: n uint64      (entries 0 .. kept - 1 hold values)
+ *   fxg_out.counters         write  FXG_NCOUNTERS uint64
+ *   fxg_run_quality_stats    d_hist: read and written, hist_cols * FXG_QS_CLASSES * FXG_QS_BINS uint64; the batch as fxg_batch above
+ *   text path (below)        d_text: read text_len + 16 bytes (the 16 are slack: their values never matter); d_line: 2 * cap_lines uint32;
+ *                            d_len, d_flags: cap_lines / lines_per_record entries; packed rows: records * stride rounded up to 16 bytes (whole
+ *                            16-byte chunks are written); d_out: text_len + records + 16 bytes; d_res, d_pk_*: records entries / the packed stream.
+ * tests/test_emu_bounds.py runs the kernels' bodies with every array against a guard page at these ends; tests/test_gpu_bounds.py surrounds every
+ * array with poison (inputs) and canaries (outputs) on the device. */
+
 typedef struct fxg_ctx fxg_ctx;
 
 /* ---- context ---- */

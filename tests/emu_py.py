@@ -105,6 +105,38 @@ def _aligned(n, dtype=np.uint8):
     return raw[off:off + n * item].view(dtype)
 
 
+PAGE = os.sysconf("SC_PAGE_SIZE")
+_GUARDED = []                    # mappings handed out by _guarded(): they live as long as the process (the bounds tier runs one case per child)
+
+
+def _guarded(n, dtype=np.uint8, where="after"):
+    """n items between guard pages: the array's contracted range (include/fxg.h: its bytes rounded up to the 16-byte granule) ends exactly at a
+    PROT_NONE page (where="after"), or starts exactly behind one (where="before"), the start 16-byte aligned either way.  Zeroed.  An emulated kernel
+    that touches a byte outside the contract on that side takes a SIGSEGV."""
+    item = np.dtype(dtype).itemsize
+    span = (n * item + 15) // 16 * 16
+    libc = C.CDLL(None, use_errno=True)
+    libc.mmap.restype, libc.mmap.argtypes = C.c_void_p, [C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_long]
+    libc.mprotect.argtypes = [C.c_void_p, C.c_size_t, C.c_int]
+    body = (span + PAGE - 1) // PAGE * PAGE
+    size = body + 2 * PAGE
+    base = libc.mmap(None, size, 3, 0x22, -1, 0)            # PROT_READ | PROT_WRITE, MAP_PRIVATE | MAP_ANONYMOUS
+    if base in (None, C.c_void_p(-1).value):
+        raise OSError(C.get_errno(), "mmap")
+    if libc.mprotect(base, PAGE, 0) != 0 or libc.mprotect(base + PAGE + body, PAGE, 0) != 0:
+        raise OSError(C.get_errno(), "mprotect")
+    start = base + PAGE + (body - span if where == "after" else 0)
+    _GUARDED.append((base, size))
+    if n == 0:
+        return np.zeros(0, dtype=dtype)
+    return np.ctypeslib.as_array((C.c_uint8 * (n * item)).from_address(start)).view(dtype)
+
+
+def _alloc(n, dtype=np.uint8, guard=None):
+    """_aligned() by default; guard="after" / "before": _guarded()"""
+    return _aligned(n, dtype) if guard is None else _guarded(n, dtype, guard)
+
+
 def hist_new():
     return lib().fxg_emu_hist_new()
 
@@ -113,18 +145,21 @@ def hist_free(h):
     lib().fxg_emu_hist_free(h)
 
 
-def run_pipeline(bases, qual, lens, params, fixed_len=None, compact=True, hist=None):
+def run_pipeline(bases, qual, lens, params, fixed_len=None, compact=True, hist=None, guard=None):
+    """guard="after" / "before": every input and output array at exactly its contracted size (include/fxg.h) against a guard page (_guarded)."""
     n, stride = bases.shape
-    b = _aligned(n * stride); b[:] = bases.reshape(-1)
+    b = _alloc(n * stride, guard=guard); b[:] = bases.reshape(-1)
     q = None
     if qual is not None:
-        q = _aligned(n * stride); q[:] = qual.reshape(-1)
+        q = _alloc(n * stride, guard=guard); q[:] = qual.reshape(-1)
     if lens is not None:
-        lens = np.ascontiguousarray(lens, dtype=np.uint16)
-    res = np.zeros(n, dtype=np.uint32)
-    ob, oq = _aligned(n * stride + 16), _aligned(n * stride + 16)
-    ol, ki, oo = np.zeros(n, dtype=np.uint16), np.zeros(n, dtype=np.uint32), np.zeros(n, dtype=np.uint64)
-    ctr = np.zeros(NCOUNTERS, dtype=np.uint64)
+        lv = _alloc(n, np.uint16, guard); lv[:] = lens
+        lens = lv
+    res = _alloc(n, np.uint32, guard)
+    cap = n * stride if guard else n * stride + 16
+    ob, oq = _alloc(cap, guard=guard), _alloc(cap, guard=guard)
+    ol, ki, oo = _alloc(n, np.uint16, guard), _alloc(n, np.uint32, guard), _alloc(n, np.uint64, guard)
+    ctr = _alloc(NCOUNTERS, np.uint64, guard)
     bt = Batch(b.ctypes.data, q.ctypes.data if q is not None else None, lens.ctypes.data if lens is not None else None,
                int(fixed_len or stride), stride, n)
     o = Out(res.ctypes.data, ob.ctypes.data if compact else None, oq.ctypes.data if (compact and q is not None) else None,
@@ -134,27 +169,33 @@ def run_pipeline(bases, qual, lens, params, fixed_len=None, compact=True, hist=N
     if rc != 0:
         raise ValueError("emu rc=%d: %s" % (rc, err.value.decode()))
     kept, nbytes = int(ctr[1]), int(ctr[2])
-    return dict(res=res, out_bases=ob[:nbytes].copy(), out_qual=oq[:nbytes].copy() if q is not None else None,
-                out_len=ol[:kept], kept_index=ki[:kept], out_off=oo[:kept], counters=ctr)
+    return dict(res=res.copy(), out_bases=ob[:nbytes].copy(), out_qual=oq[:nbytes].copy() if q is not None else None,
+                out_len=ol[:kept].copy(), kept_index=ki[:kept].copy(), out_off=oo[:kept].copy(), counters=ctr.copy())
 
 
-def run_quality_stats(bases, qual, lens, fixed_len=None, hist=None, cols=None):
-    """Adds the batch to hist[cols][5][128] (uint64) and returns it."""
+def run_quality_stats(bases, qual, lens, fixed_len=None, hist=None, cols=None, guard=None):
+    """Adds the batch to hist[cols][5][128] (uint64) and returns it.  guard: as in run_pipeline (the histogram too)."""
     n, stride = bases.shape
     cols = cols or stride
     if hist is None:
         hist = np.zeros((cols, 5, 128), dtype=np.uint64)
-    b = _aligned(n * stride); b[:] = bases.reshape(-1)
+    h = hist
+    if guard:
+        h = _guarded(hist.size, np.uint64, guard).reshape(hist.shape); h[:] = hist
+    b = _alloc(n * stride, guard=guard); b[:] = bases.reshape(-1)
     q = None
     if qual is not None:
-        q = _aligned(n * stride); q[:] = qual.reshape(-1)
+        q = _alloc(n * stride, guard=guard); q[:] = qual.reshape(-1)
     if lens is not None:
-        lens = np.ascontiguousarray(lens, dtype=np.uint16)
+        lv = _alloc(n, np.uint16, guard); lv[:] = lens
+        lens = lv
     bt = Batch(b.ctypes.data, q.ctypes.data if q is not None else None, lens.ctypes.data if lens is not None else None,
                int(fixed_len or stride), stride, n)
-    rc = lib().fxg_emu_run_quality_stats(C.byref(bt), hist.ctypes.data, hist.shape[0])
+    rc = lib().fxg_emu_run_quality_stats(C.byref(bt), h.ctypes.data, h.shape[0])
     if rc != 0:
         raise ValueError("emu quality_stats rc=%d" % rc)
+    if h is not hist:
+        hist[:] = h
     return hist
 
 
@@ -170,3 +211,67 @@ def last_plan():
     a, t = C.c_int(), C.c_int()
     lib().fxg_emu_last_plan(C.byref(a), C.byref(t))
     return a.value, bool(t.value)
+
+
+# ---- the device text path (fxg_text.h) through fxg_emu_fastq_index / _pack / _format / fxg_emu_fasta_weights ----
+class TextInfo(C.Structure):
+    _fields_ = [("lines", C.c_uint64), ("records", C.c_uint64), ("consumed", C.c_uint64), ("max_len", C.c_uint32),
+                ("min_len", C.c_uint32), ("irregular", C.c_uint32), ("first_bad", C.c_uint32), ("numeric_records", C.c_uint32),
+                ("has_cr", C.c_uint32)]
+
+
+def fastq_index(text, at_eof=True, lpr=4, cap_records=None, guard=None):
+    """fxg_fastq_index over `text` (the caller appends the final newline, as the engine does at end of input).  The text array is the contracted
+    text_len + 16 bytes, the line / length / flag arrays the contracted cap_lines and cap_records entries (include/fxg.h)."""
+    cap_records = cap_records or (len(text) // (4 if lpr == 2 else 7) + 2)
+    cap_lines = lpr * cap_records + 1
+    t = _alloc(len(text) + 16, guard=guard)
+    t[:len(text)] = np.frombuffer(text, dtype=np.uint8)
+    line, lens, flags = _alloc(2 * cap_lines, np.uint32, guard), _alloc(cap_records, np.uint16, guard), _alloc(cap_records, np.uint8, guard)
+    state, info = C.create_string_buffer(256), TextInfo()
+    rc = lib().fxg_emu_fastq_index(state, C.c_void_p(t.ctypes.data), C.c_uint64(len(text)), C.c_int(int(at_eof)), C.c_int(lpr),
+                                   C.c_void_p(line.ctypes.data), C.c_uint64(cap_lines), C.c_void_p(lens.ctypes.data), C.c_void_p(flags.ctypes.data), C.byref(info))
+    if rc != 0:
+        raise ValueError("emu fastq_index rc=%d" % rc)
+    return dict(text=t, text_len=len(text), lpr=lpr, line=line, cap_lines=cap_lines, lens=lens, flags=flags, info=info)
+
+
+def fastq_pack(ix, n, stride, qoffset=33, want_qual=True, guard=None):
+    """fxg_fastq_pack into rows of the contracted n * stride bytes (rounded up to 16)."""
+    want_qual = want_qual and ix["lpr"] == 4
+    b = _alloc(n * stride, guard=guard)
+    q = _alloc(n * stride, guard=guard) if want_qual else None
+    irr = C.c_uint32()
+    rc = lib().fxg_emu_fastq_pack(C.c_void_p(ix["text"].ctypes.data), C.c_uint64(ix["text_len"]), C.c_int(ix["lpr"]), C.c_void_p(ix["line"].ctypes.data),
+                                  C.c_uint64(ix["cap_lines"]), C.c_void_p(ix["flags"].ctypes.data), C.c_uint64(n), C.c_uint32(stride), C.c_int(qoffset),
+                                  C.c_void_p(b.ctypes.data), C.c_void_p(q.ctypes.data if q is not None else None), C.byref(irr))
+    if rc != 0:
+        raise ValueError("emu fastq_pack rc=%d" % rc)
+    return b.reshape(n, stride).copy(), (q.reshape(n, stride).copy() if q is not None else None), irr.value
+
+
+def fastq_format(ix, n, res, rows_qual=None, stride=0, qoffset=33, out_fasta=False, guard=None):
+    """fxg_fastq_format of the forward slices (no packed arrays) into the contracted text_len + records + 16 bytes; returns the bytes written."""
+    r = _alloc(n, np.uint32, guard); r[:] = res
+    rq = None
+    if rows_qual is not None:
+        rq = _alloc(rows_qual.size, guard=guard); rq[:] = rows_qual.reshape(-1)
+    out = _alloc(ix["text_len"] + n + 16, guard=guard)
+    nb = C.c_uint64()
+    rc = lib().fxg_emu_fastq_format(C.c_void_p(ix["text"].ctypes.data), C.c_int(ix["lpr"]), C.c_void_p(ix["line"].ctypes.data), C.c_uint64(ix["cap_lines"]),
+                                    C.c_void_p(ix["flags"].ctypes.data), C.c_uint64(n), C.c_void_p(r.ctypes.data), C.c_uint32(0), C.c_int(0),
+                                    None, None, None, C.c_void_p(rq.ctypes.data if rq is not None else None), C.c_uint32(stride), C.c_int(qoffset),
+                                    C.c_int(int(out_fasta)), C.c_void_p(out.ctypes.data), C.byref(nb))
+    if rc != 0:
+        raise ValueError("emu fastq_format rc=%d" % rc)
+    return out[:nb.value].tobytes()
+
+
+def fasta_weights(ix, n, res, guard=None):
+    r = _alloc(n, np.uint32, guard); r[:] = res
+    w = (C.c_uint64 * 8)()
+    rc = lib().fxg_emu_fasta_weights(C.c_void_p(ix["text"].ctypes.data), C.c_void_p(ix["line"].ctypes.data), C.c_uint64(ix["cap_lines"]), C.c_uint64(n),
+                                     C.c_void_p(r.ctypes.data), w)
+    if rc != 0:
+        raise ValueError("emu fasta_weights rc=%d" % rc)
+    return list(w)
