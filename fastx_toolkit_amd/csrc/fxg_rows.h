@@ -4,8 +4,9 @@
 // Why a second kernel for the same stages (fxg_kernel_tiles<0,0> stays the general form: any read length, every other stage):
 // the tile kernel decides from the quality rows, then waits for the tile's place in the output (a prefix over all earlier tiles)
 // and gathers the kept prefixes from HBM -- it fetches the quality rows twice and the bases at cache-line granularity around every
-// kept read: 27.4 GB through the L2s per cfg2 launch against 22.3 GB of input + output.  Here every byte crosses the fabric once
-// (rocprofv3 PMC: 15.2 GB read + 7.7 GB written, profiles/pmc_traffic.json, r02_rows_pmc/):
+// kept read: 27.4 GB through the L2s per cfg2 launch against 22.3 GB of input + output.  Here every quality byte crosses the fabric once
+// and of the base rows only the 16-byte chunks that hold kept prefixes (the full fetch, FXG_ROWS_SPARSE_BASES=0: 15.2 GB read + 7.5 GB
+// written, profiles/full_bases_pmc_traffic_cfg2.json; the sparse one: profiles/pmc_traffic_cfg2.json):
 //   stage A, tile `cur`:  the quality rows come in by LDS-DMA (buffer_load ... lds, 1 KB per wave instruction) and are transposed
 //      through a 9.6 KB staging buffer: lane r holds read r (38 dwords for 150 bases, v_alignbyte_b32).  The lane builds its read's
 //      threshold bitmap in registers (v_dot4_u32_u8 gathers the compare flags), decides it, the wave scans (keep, length) with DPP
@@ -13,17 +14,19 @@
 //   stage B, tile `pend` (decided one step earlier; its quality rows waited in registers): the tile's place in the output has
 //      arrived; every lane writes its kept prefix into the staging buffer at its offset in the tile's packed output, and the wave
 //      stores the packed bytes as whole, aligned 16-byte units of the global array (fxg_rows_flush).  The base rows take the same
-//      road: LDS-DMA, transpose, pack, flush.
-// A workgroup IS one wave: no workgroup barrier anywhere, no gather tables, no second pass.  Twelve waves per CU (138 VGPRs).
-// Measured against fxg_kernel_tiles<0,0> on the same box it is 3-4 % faster (4.03 against 4.16-4.19 ms for cfg2), not the 18 % the
-// bytes suggest: both sit at what the memory system gives this read : write mix -- a plain streaming kernel that reads 15 GB and writes 7.3 GB, nothing
-// else, takes 4.25-4.5 ms (scripts/ubench/mix_rw.hip, profiles/r02/z_mix_rw.txt); read alone 2.34 ms, write alone 1.18 ms.
+//      road: LDS-DMA, transpose, pack, flush -- but the tile is decided by then, and the DMA skips every chunk that holds no byte of a
+//      kept prefix (fxg_rows_need_mask): on cfg2 a third of the reads are dropped and the kept ones trimmed to 71 of 150 bases on average.
+// A workgroup IS one wave: no workgroup barrier anywhere, no gather tables, no second pass.  Twelve waves per CU (141 VGPRs).
+// With the full base fetch it was 3-4 % faster than fxg_kernel_tiles<0,0> on the same box (4.03 against 4.16-4.19 ms for cfg2), not the 18 % the
+// bytes suggest: both sat at what the memory system gives this read : write mix for the bytes they moved -- a plain streaming kernel that reads
+// 15 GB and writes 7.3 GB, nothing else, takes 4.25-4.5 ms (scripts/ubench/mix_rw.hip, profiles/r02/z_mix_rw.txt); read alone 2.34 ms, write
+// alone 1.18 ms.  So the lever left was fewer bytes, not a faster stream of the same ones: the sparse base fetch.
 #pragma once
 #include "fxg_kernels.h"
 
 #define FXG_ROWS_T 64u                  // reads per tile = lanes per wave
 #ifndef FXG_ROWS_LB
-#define FXG_ROWS_LB 3                   // waves per SIMD (__launch_bounds__): two tiles' quality rows live in registers; the kernel uses 138 VGPRs of the 168 this allows
+#define FXG_ROWS_LB 3                   // waves per SIMD (__launch_bounds__): two tiles' quality rows live in registers; <38,1> uses 141 VGPRs of the 168 this allows
 #endif
 #ifndef FXG_ROWS_SCAN_K
 #define FXG_ROWS_SCAN_K 8               // tiles per scanner batch / 64 (fxg_scanner_multi)
@@ -35,6 +38,11 @@
 #ifndef FXG_ROWS_NSCAN
 #define FXG_ROWS_NSCAN 8                // scanner waves
 #endif
+#ifndef FXG_ROWS_SPARSE_BASES
+#define FXG_ROWS_SPARSE_BASES 1         // stage B fetches only the 16-byte chunks of the base rows that hold kept-prefix bytes (fxg_rows_need_mask); 0: every row whole (the A/B arm);
+                                        // 2: fxg_kernel_rows_multi too -- off by default: 3-4 % slower at 36 and 50 bases, level at 76
+#endif
+#define FXG_ROWS_SPARSE_MULTI (FXG_ROWS_SPARSE_BASES >= 2)
 
 // staging buffer: the tile's rows + slack (every lane reads and packs a full register row, up to 156 bytes, whatever the stride)
 __host__ __device__ inline u32 fxg_rows_lds(u32 stride, u32 lanes_per_read = 1u, u32 reads_per_lane = 1u) { return fxg_r16(FXG_ROWS_T * reads_per_lane / lanes_per_read * stride) + 176u; }
@@ -141,6 +149,62 @@ FXG_HD u32 fxg_rows_decide(const FxgKArgs &a, const u32 (&q)[NW], u32 read, u32 
 // the piece lengths of a read of `len` bytes split at HB = 4 NW
 FXG_HD u32 fxg_rows_piece_len(u32 len, u32 HB, u32 h) { return h == 0u ? (len < HB ? len : HB) : (len > HB ? len - HB : 0u); }
 
+// ---- which chunks of a tile's base rows stage B needs (FXG_ROWS_SPARSE_BASES) ----
+// When stage B runs, every read of the pending tile is decided: only the bytes [r stride, r stride + klen(r)) of kept reads reach an output,
+// 71 of 150 bytes per read on cfg2 (a third of the reads dropped, the rest trimmed).  The base fetch skips every 16-byte LDS-DMA chunk that holds
+// none of them.  The quality fetch of stage A stays whole: the decision needs every byte.
+// klen(r) -- the read's kept length, 0 when it is dropped -- sits in a word of the lane(s) that hold read r and comes over by ds_bpermute:
+//   H = 1: lane r;   H = 2: lane 2 r (the read's whole kept length, both pieces);   R > 1: byte r / 64 of lane r mod 64 (rows < 80 bytes: klen < 256)
+// Strides are >= 28 > 16, so a chunk touches at most two rows: r_lo = floor(b0 / stride) and r_hi = floor(b1 / stride).  Read r_lo's prefix
+// starts at or before b0 and overlaps the chunk iff b0 < start + klen; read r_hi (!= r_lo) starts inside the chunk and overlaps it iff klen > 0.
+// Why the chunks left out cannot change a result: the staging buffer still holds the quality pack of the same step there.  A lane reads its
+// row whole but packs only its first olen bytes, all of which lie in fetched chunks; the unpredicated (`fast`) pack writes the bytes past
+// olen only into dwords that a later lane overwrites or past the tile's totb, which fxg_rows_flush never stores (fxg_rows_pack).
+
+// exact floor(x / d) by one multiply-high, d uniform: m = ceil(2^32 / d), m d = 2^32 + e with 0 <= e < d, so x m / 2^32 = x / d + x e / (d 2^32)
+// and the quotient is exact while x e < 2^32 -- here x < 2^14 (tile offsets) and d <= 304
+FXG_HD u32 fxg_rows_magic(u32 d) { return 0xFFFFFFFFu / d + 1u; }
+#ifdef FXG_HOST_EMULATION
+FXG_HD u32 fxg_rows_div(u32 x, u32 m) { return (u32)(((u64)x * m) >> 32); }
+#else
+FXG_HD u32 fxg_rows_div(u32 x, u32 m) { return __umulhi(x, m); }
+#endif
+// read r's kept length from the word `w` that lane fxg_rows_klen_lane(r) holds; reads past the tile (r >= TR) have none
+template <int H, int R>
+FXG_HD u32 fxg_rows_klen_lane(u32 r) { return R > 1 ? r & (FXG_ROWS_T - 1u) : r * (u32)H; }
+template <int H, int R>
+FXG_HD u32 fxg_rows_klen_pick(u32 w, u32 r) { return R > 1 ? (w >> (8u * (r / FXG_ROWS_T))) & 0xFFu : w; }
+// does the tile byte range [b0, b1] (b1 - b0 < stride) overlap a kept prefix?  perm(l) = the klen word of lane l (ds_bpermute on the device):
+// both calls are made by every lane, whatever the answer
+template <int H, int R, class PERM>
+FXG_HD bool fxg_rows_needed(u32 b0, u32 b1, u32 stride, u32 magic, PERM perm)
+{
+    constexpr u32 TR = FXG_ROWS_T * (u32)R / (u32)H;
+    const u32 r_lo = fxg_rows_div(b0, magic), r_hi = fxg_rows_div(b1, magic);
+    const u32 w_lo = perm(fxg_rows_klen_lane<H, R>(r_lo)), w_hi = perm(fxg_rows_klen_lane<H, R>(r_hi));
+    const u32 k_lo = r_lo < TR ? fxg_rows_klen_pick<H, R>(w_lo, r_lo) : 0u, k_hi = r_hi < TR ? fxg_rows_klen_pick<H, R>(w_hi, r_hi) : 0u;
+    return b0 < r_lo * stride + k_lo || (r_hi != r_lo && k_hi != 0u);
+}
+// bit K: the chunk this lane fetches with wave load K (tile bytes [1024 K + 16 lane, + 16)) is needed, K < NC (fxg_rows_fetch);
+// bit 31: the byte this lane fetches in a tile that ends inside a dword (tile byte (tbytes & ~3) + lane, lanes below tbytes & 3)
+#define FXG_ROWS_TAIL_BIT (1u << 31)
+template <int NC, int H, int R, class PERM>
+FXG_HD u32 fxg_rows_need_mask(u32 lane, u32 stride, u32 magic, u32 tbytes, PERM perm)
+{
+    static_assert(NC < 31, "a bit per wave load and the tail bit");
+    u32 m = 0;
+#pragma unroll
+    for (int K = 0; K < NC; ++K) {
+        const u32 b0 = 1024u * (u32)K + 16u * lane;
+        m |= fxg_rows_needed<H, R>(b0, b0 + 15u, stride, magic, perm) ? 1u << K : 0u;
+    }
+    if (tbytes & 3u) {                  // (wave-uniform) only a batch's last tile
+        const u32 x = (tbytes & ~3u) + lane;
+        m |= fxg_rows_needed<H, R>(x, x, stride, magic, perm) ? FXG_ROWS_TAIL_BIT : 0u;
+    }
+    return m;
+}
+
 #ifndef FXG_HOST_EMULATION
 // A workgroup is ONE wave: its LDS accesses execute in order, so "every lane's reads / writes before this point are done" needs no
 // barrier, only the wave's own LDS counter at zero and the compiler kept from moving accesses across the point.
@@ -153,18 +217,24 @@ typedef __attribute__((address_space(3))) unsigned char fxg_lds_u8;     // the s
 // wave load K = bytes [1024 K, 1024 K + 1024): 4096 (K / 4) in the lane's offset, 1024 (K % 4) in the instruction's (a compile-time
 // field) -- both are range-checked against the tile's bytes (a scalar offset would not be) and the instruction offset also moves the
 // LDS side
-template <int K, int NC>
-__device__ __forceinline__ void fxg_rows_fetch_from(__amdgpu_buffer_rsrc_t rs, fxg_lds_u8 *sbuf, u32 lane, u32 nck, u32 room)
+// SPARSE: `need` (fxg_rows_need_mask) -- a lane whose bit K is clear stays out of wave load K.  Not SPARSE: the condition of the whole
+// fetch, word for word (the compiler shapes the two differently, and the whole one is the faster for a whole fetch)
+template <int K, int NC, bool SPARSE>
+__device__ __forceinline__ void fxg_rows_fetch_from(__amdgpu_buffer_rsrc_t rs, fxg_lds_u8 *sbuf, u32 lane, u32 nck, u32 room, u32 need)
 {
     typedef __attribute__((address_space(3))) void lptr_t;
     if constexpr (K < NC) {
         // the last wave load of a tile may reach past the buffer's rows (64 rows are seldom whole KBs): those lanes stay out
-        if ((u32)K < nck && ((u32)(K + 1) * 1024u <= room || (u32)K * 1024u + (lane << 4) < room)) __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (lptr_t *)(sbuf + (K >> 2) * 4096), 16, (int)(lane << 4) + (K >> 2) * 4096, 0, (K & 3) * 1024, FXG_ROWS_LD_AUX);
-        fxg_rows_fetch_from<K + 1, NC>(rs, sbuf, lane, nck, room);
+        if constexpr (SPARSE) {
+            if ((u32)K < nck && ((need >> K) & 1u) && ((u32)(K + 1) * 1024u <= room || (u32)K * 1024u + (lane << 4) < room)) __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (lptr_t *)(sbuf + (K >> 2) * 4096), 16, (int)(lane << 4) + (K >> 2) * 4096, 0, (K & 3) * 1024, FXG_ROWS_LD_AUX);
+        } else {
+            if ((u32)K < nck && ((u32)(K + 1) * 1024u <= room || (u32)K * 1024u + (lane << 4) < room)) __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (lptr_t *)(sbuf + (K >> 2) * 4096), 16, (int)(lane << 4) + (K >> 2) * 4096, 0, (K & 3) * 1024, FXG_ROWS_LD_AUX);
+        }
+        fxg_rows_fetch_from<K + 1, NC, SPARSE>(rs, sbuf, lane, nck, room, need);
     }
 }
-template <int NW>
-__device__ __forceinline__ void fxg_rows_fetch(const uint8_t *src, u64 tb, u32 tbytes, fxg_lds_u8 *sbuf, u32 lane)
+template <int NW, bool SPARSE = false>
+__device__ __forceinline__ void fxg_rows_fetch(const uint8_t *src, u64 tb, u32 tbytes, fxg_lds_u8 *sbuf, u32 lane, u32 need = ~0u)
 {
     constexpr int NC = (NW * 4 + 15) / 16;            // chunks per lane: 64 lanes x NC x 16 bytes cover 64 rows of up to 4 NW bytes
     const u32 nck = (tbytes + 1023u) >> 10;           // wave loads this tile needs (uniform)
@@ -172,8 +242,17 @@ __device__ __forceinline__ void fxg_rows_fetch(const uint8_t *src, u64 tb, u32 t
     // last 1-3 bytes come in by byte loads, so nothing past the arrays is ever read
     const u32 whole = tbytes & ~3u;
     const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void *)(src + tb), 0, (int)whole, 0x00020000);
-    fxg_rows_fetch_from<0, NC>(rs, sbuf, lane, nck, fxg_r16(tbytes));
-    if (whole != tbytes && lane < tbytes - whole) sbuf[whole + lane] = src[tb + whole + lane];
+    fxg_rows_fetch_from<0, NC, SPARSE>(rs, sbuf, lane, nck, fxg_r16(tbytes), need);
+    if (whole != tbytes && lane < tbytes - whole && (!SPARSE || (need & FXG_ROWS_TAIL_BIT))) sbuf[whole + lane] = src[tb + whole + lane];
+}
+// the mask of the base fetch (fxg_rows_need_mask) from `kw`, this lane's klen word (the table above fxg_rows_klen_lane)
+template <int NW, int H, int R>
+__device__ __forceinline__ u32 fxg_rows_base_need(u32 kw, u32 lane, u32 stride, u32 magic, u32 tbytes)
+{
+    constexpr int NC = (NW * R * 4 + 15) / 16;
+    static_assert(R == 1 || 4 * NW < 256, "several reads per lane: one byte of the klen word per read");
+    const auto perm = [kw](u32 l) { return (u32)__builtin_amdgcn_ds_bpermute((int)(l << 2), (int)kw); };
+    return fxg_rows_need_mask<NC, H, R>(lane, stride, magic, tbytes, perm);
 }
 __device__ __forceinline__ void fxg_rows_landed()
 {
@@ -302,6 +381,9 @@ __global__ __launch_bounds__(64, FXG_ROWS_LB) void fxg_kernel_rows(const FxgKArg
     fxg_lds_u8 *lsm = (fxg_lds_u8 *)smem;
     u32 lane = threadIdx.x;
     const u32 stride = a.stride;
+#if FXG_ROWS_SPARSE_BASES
+    const u32 magic = fxg_rows_magic(stride);
+#endif
     // the first a.nscan workgroups (= waves) to get here turn the tiles' totals into prefixes; the others process tiles
     u32 role = 0;
     if (lane == 0) role = atomicAdd(a.role, 1u);
@@ -412,10 +494,20 @@ __global__ __launch_bounds__(64, FXG_ROWS_LB) void fxg_kernel_rows(const FxgKArg
             }
             FXG_WAVE_SYNC();                                                  // the buffer is free again
             FXG_PHASE(3);
-            // the base rows take the same road: HBM -> staging buffer -> registers -> packed -> out
-            if (!FXG_DBG(a, 4u)) {
+            // the base rows take the same road: HBM -> staging buffer -> registers -> packed -> out -- only the chunks that hold kept
+            // prefixes (FXG_ROWS_SPARSE_BASES), nothing at all for a tile that keeps no byte or was not placed
+            if (!FXG_DBG(a, 4u) && (!FXG_ROWS_SPARSE_BASES || (placed && p_totb != 0u))) {
                 u32 b[NW];
-                fxg_rows_fetch<NW>(a.bases, tb, tbytes, lsm, lane);
+                u32 need = ~0u;
+#if FXG_ROWS_SPARSE_BASES
+                u32 kw = keep ? olen : 0u;                                    // klen word: H = 1, the lane's own read
+                if constexpr (H == 2) {                                       // lane 2r: the read's kept length, both pieces
+                    const u32 oo = (u32)__builtin_amdgcn_mov_dpp((int)olen, 0xB1, 0xf, 0xf, true);
+                    kw = keep && hf == 0u ? olen + oo : 0u;
+                }
+                need = fxg_rows_base_need<NW, H, 1>(kw, lane, stride, magic, tbytes);
+#endif
+                fxg_rows_fetch<NW, FXG_ROWS_SPARSE_BASES != 0>(a.bases, tb, tbytes, lsm, lane, need);
                 fxg_rows_landed();
                 FXG_PHASE(4);
                 fxg_rows_read<NW>(smem, rd * stride + hf * HB, b);
@@ -462,6 +554,9 @@ __global__ __launch_bounds__(64, FXG_ROWS_LB) void fxg_kernel_rows_multi(const F
     fxg_lds_u8 *lsm = (fxg_lds_u8 *)smem;
     u32 lane = threadIdx.x;
     const u32 stride = a.stride;
+#if FXG_ROWS_SPARSE_MULTI
+    const u32 magic = fxg_rows_magic(stride);
+#endif
     u32 role = 0;
     if (lane == 0) role = atomicAdd(a.role, 1u);
     role = (u32)__builtin_amdgcn_readfirstlane((int)role);
@@ -545,20 +640,29 @@ __global__ __launch_bounds__(64, FXG_ROWS_LB) void fxg_kernel_rows_multi(const F
                 if (keep) fxg_write_kept_meta(a, bc[0] + p_exc[j], olen, r0 + (u32)j * FXG_ROWS_T + lane, bc[1] + exb);
             }
             FXG_WAVE_SYNC();                                                  // the buffer is free again
-            u32 b[R][NW];
-            fxg_rows_fetch<NW * R>(a.bases, tb, tbytes, lsm, lane);
-            fxg_rows_landed();
+            if (!FXG_ROWS_SPARSE_MULTI || (placed && p_totb != 0u)) {
+                u32 b[R][NW];
+                u32 need = ~0u;
+#if FXG_ROWS_SPARSE_MULTI
+                u32 kw = 0;                                                   // klen word: byte j = kept length of the lane's read in sub-tile j (< 80)
 #pragma unroll
-            for (int j = 0; j < R; ++j) fxg_rows_read<NW>(smem, ((u32)j * FXG_ROWS_T + lane) * stride, b[j]);
-            FXG_WAVE_SYNC();
+                for (int j = 0; j < R; ++j) kw |= (p_info[j] >> 31 ? (p_info[j] >> 16) & 0x7FFFu : 0u) << (8 * j);
+                need = fxg_rows_base_need<NW, 1, R>(kw, lane, stride, magic, tbytes);
+#endif
+                fxg_rows_fetch<NW * R, FXG_ROWS_SPARSE_MULTI>(a.bases, tb, tbytes, lsm, lane, need);
+                fxg_rows_landed();
 #pragma unroll
-            for (int j = 0; j < R; ++j) {
-                const u32 keep = placed ? p_info[j] >> 31 : 0u, olen = (p_info[j] >> 16) & 0x7FFFu, exb = p_info[j] & 0xFFFFu;
-                if (keep) fxg_rows_pack<NW>(smem, exb, b[j], olen, fast);
+                for (int j = 0; j < R; ++j) fxg_rows_read<NW>(smem, ((u32)j * FXG_ROWS_T + lane) * stride, b[j]);
+                FXG_WAVE_SYNC();
+#pragma unroll
+                for (int j = 0; j < R; ++j) {
+                    const u32 keep = placed ? p_info[j] >> 31 : 0u, olen = (p_info[j] >> 16) & 0x7FFFu, exb = p_info[j] & 0xFFFFu;
+                    if (keep) fxg_rows_pack<NW>(smem, exb, b[j], olen, fast);
+                }
+                FXG_WAVE_SYNC();
+                if (placed) fxg_rows_flush(a.out_bases, bc[1], p_totb, smem, lane);
+                FXG_WAVE_SYNC();
             }
-            FXG_WAVE_SYNC();
-            if (placed) fxg_rows_flush(a.out_bases, bc[1], p_totb, smem, lane);
-            FXG_WAVE_SYNC();
         }
         if (!havec) break;
 #pragma unroll

@@ -169,7 +169,9 @@ typedef struct fxg_out {
 /* Memory contract: the bytes a kernel may touch through each pointer, counted from the pointer.  "Granule": the 16-byte aligned block that holds
  * an array's last byte.  An input may be read up to the end of that granule (aligned 16-byte loads; a granule never crosses a page), and what is
  * read there never reaches a result.  Nothing before a pointer is read, and nothing outside an output's range is written.
- *   fxg_batch.bases, .qual   read   n * stride bytes (+ granule)      every row whole, also past len[r]; qual may be NULL
+ *   fxg_batch.bases, .qual   read   n * stride bytes (+ granule)      every row whole, also past len[r]; qual may be NULL.  A kernel may read
+ *                                                                       less: the rows kernels fetch only the 16-byte chunks of .bases that
+ *                                                                       hold kept prefixes (fxg_rows.h, FXG_ROWS_SPARSE_BASES)
  *   fxg_batch.len            read   n uint16 (+ granule)               NULL: every read is fixed_len long
  *   fxg_out.res              write  n uint32
  *   fxg_out.out_bases, .out_qual   write  n * stride bytes            the capacity; the kept reads fill counters[FXG_C_KEPT_BASES] <= n * stride of it

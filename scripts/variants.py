@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """A/B compile-time kernel variants: `build` (here, hipcc cross-compiles) then `run` (GPU box) times cfg2 with each library.
 
-    python scripts/variants.py build            # fastx_toolkit_amd/libfxg_v_<name>.so, git-ignored, travel with gpurun
+    python scripts/variants.py build [name ...] # fastx_toolkit_amd/libfxg_v_<name>.so, git-ignored
     python scripts/variants.py run              # one JSON line per variant (scripts/ablate.py in a subprocess each)
 """
 import json
@@ -18,6 +18,8 @@ VARIANTS = {            # edit freely: every entry becomes fastx_toolkit_amd/lib
     "abl_nonts": ["-DFXG_ABLATION", "-DFXG_V_NO_NTS"],
     "abl_ldnt": ["-DFXG_ABLATION", "-DFXG_ROWS_LD_AUX=2"],
     "abl_ldnt_nonts": ["-DFXG_ABLATION", "-DFXG_ROWS_LD_AUX=2", "-DFXG_V_NO_NTS"],
+    "full_bases": ["-DFXG_ROWS_SPARSE_BASES=0"],       # the rows kernels' stage B fetches every base row whole (before the sparse fetch)
+    "sparse_multi": ["-DFXG_ROWS_SPARSE_BASES=2"],     # the sparse base fetch in fxg_kernel_rows_multi too
 }
 
 
@@ -25,10 +27,10 @@ def lib(name):
     return os.path.join(_b.PKG, "libfxg_v_%s.so" % name)
 
 
-if sys.argv[1] == "build":
-    procs = [(n, subprocess.Popen([_b.hipcc()] + _b.HIPCC_FLAGS + d + [os.path.join(_b.CSRC, "fxg_engine.hip"), "-o", lib(n)])) for n, d in VARIANTS.items()]
-    for n, p in procs:
-        print(n, "rc", p.wait())
+if sys.argv[1] == "build":             # python scripts/variants.py build [name ...]: the engine's own split build and ISA check, one variant after the other
+    for n in (sys.argv[2:] or VARIANTS):
+        _b.compile_engine(lib(n), VARIANTS[n])
+        print(n, "built", flush=True)
 else:
     cfgs = os.environ.get("ABLATE") or json.dumps([["full", {}], ["decision-only", {}, False]])
     for n in (os.environ.get("VARIANTS", "").split() or VARIANTS):
