@@ -7,9 +7,15 @@ on 50 M synthetic 150 bp Phred+33 reads PER GPU (seed 2, SURVEY.md 8d generator,
 device so inputs are resident in HBM when the timed region starts), fused into ONE pass that also
 stream-compacts the kept, trimmed reads in input order.  One "step" = one such pass over the batch.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--reads R] [--config cfg2|cfg3|cfg4|cfg5shard|stats] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--reads R] [--config cfg2|cfg3|cfg4|cfg5shard|stats] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
            bench.py --gpus N --steps K --warmup W
+
+A plain run does only what the headline line needs: it generates the inputs on the device, warms up, times the steps, writes
+--dump-outputs and prints the line (value, roofline and self-check of the timed launches themselves).  --full adds what takes
+runs of its own, after the headline's measurement and without touching its keys: the reference's CPU rate on a bounded sample
+(cpu_baseline; --no-cpu-baseline drops it), the other BASELINE configs at their stated sizes (configs and roofline.other_configs,
+cfg2 at its own size only; --headline-only drops them) and the command-line tools end to end (e2e, cfg2 only; --no-e2e drops it).
 
 --config selects another BASELINE.json configuration (same JSON shape, its own roofline object):
     cfg3       fastx_clipper -a AGATCGGAAGAGC -l 15 -n, 50 M x 100 bp                (VALU-bound: GCUPS)
@@ -585,12 +591,13 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--config", choices=sorted(CONFIGS), default="cfg2")
     ap.add_argument("--reads", type=int, default=0, help="reads per GPU (default: the configuration's size)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-e2e", action="store_true")
+    ap.add_argument("--full", action="store_true", help="after the headline: the CPU baseline, the other BASELINE configs and the tools end to end (one GPU)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--no-e2e", action="store_true", help="--full without the tools end to end")
     ap.add_argument("--e2e", action="store_true", help="also time the config's command line end to end, one tool chain per GPU (weak scaling; any --gpus)")
     ap.add_argument("--e2e-reads", type=int, default=32_000_000, help="reads per rank of the --e2e leg")
     ap.add_argument("--decision-only", action="store_true", help="no compaction: 154 B/read variant (not the headline)")
-    ap.add_argument("--headline-only", action="store_true", help="the default config alone, without the other BASELINE configs behind it")
+    ap.add_argument("--headline-only", action="store_true", help="--full without the other BASELINE configs")
     ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed step's outputs of the measured config as DIR/<name>.npy")
     args = ap.parse_args()
     if args.steps < 1:
@@ -814,13 +821,14 @@ def main():
         return None
 
     out = measure(args.config, args.steps, args.warmup, args.reads, args.e2e, dump=args.dump_outputs)
+    # Everything below takes runs of its own (about 160 s on one MI355X; a whole plain run takes about 3 s), so it is done with --full only.
     if rank == 0:
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(args.config)
-        # Every BASELINE config in the one invocation the driver times (round-4 verdict item 3): after the headline line's own measurement the other
+        # Every BASELINE config in one invocation (round-4 verdict item 3): after the headline line's own measurement the other
         # workloads run in this process at their stated sizes (buffers freed in between: config 4 alone needs 120 GB), each with its roofline object,
         # its self-check against the oracle-verified tuple and the reference's CPU rate on a bounded sample.  The headline keys stay what they were.
-        if world == 1 and args.config == "cfg2" and not args.reads and not args.decision_only and not args.headline_only:
+        if world == 1 and args.full and args.config == "cfg2" and not args.reads and not args.decision_only and not args.headline_only:
             out["configs"] = {}
             for c in ("cfg3", "cfg4", "cfg5shard", "stats"):
                 torch.cuda.empty_cache()
@@ -848,7 +856,7 @@ def main():
                 except Exception as e:                     # a failing extra config must not take the headline line down -- but it must be seen
                     out["configs"][c] = {"error": repr(e)[:300]}
             torch.cuda.empty_cache()
-        if world == 1 and not args.no_e2e and args.config == "cfg2":
+        if world == 1 and args.full and not args.no_e2e and args.config == "cfg2":
             try:
                 with _on_gpu_node(local) as place:
                     out["e2e"] = e2e_leg()

@@ -494,6 +494,28 @@ def test_bench_two_ranks_on_one_gpu_via_gloo():
     assert (er["kept_reads"], er["output_bytes"], er["output_md5"]) == (e1["kept_reads"], e1["output_bytes"], e1["output_md5"]) and er["output_md5"], (er, e1)
 
 
+def test_bench_plain_run_is_the_headline_alone():
+    """A plain bench run measures the headline and nothing else; --full adds the legs that take runs of their own after it
+    (here the CPU baseline: with --reads the other configs are skipped, and --no-e2e drops the tools end to end)."""
+    import json
+    import subprocess
+    import sys
+    from conftest import ROOT
+    base = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--reads", "2000000"]
+    lines = {}
+    for name, extra in (("plain", []), ("full", ["--full", "--no-e2e"])):
+        p = subprocess.run(base + extra, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
+        assert p.returncode == 0, p.stderr[-2000:]
+        lines[name] = json.loads([l for l in p.stdout.decode().splitlines() if l.startswith("{")][-1])
+    for d in lines.values():
+        assert d["unit"] == "Mreads/s" and d["value"] > 0 and d["ms_per_step"] > 0 and d["higher_is_better"] is True and d["dtype"] == "u8", d
+        assert d["config"]["reads_per_gpu"] == 2000000 and d["roofline"]["bound"] == "hbm" and "self_check" in d
+    plain, full = lines["plain"], lines["full"]
+    assert not {"cpu_baseline", "configs", "e2e", "e2e_ranks"} & set(plain) and "other_configs" not in plain["roofline"], sorted(plain)
+    assert "cpu_baseline" in full and not {"configs", "e2e"} & set(full), sorted(full)
+    assert (plain["config"]["kept_reads_per_gpu"], plain["self_check"]["checksum"]) == (full["config"]["kept_reads_per_gpu"], full["self_check"]["checksum"])
+
+
 @pytest.mark.parametrize("cfg", ["cfg2", "cfg3", "cfg5"])
 def test_engine_shards_reassemble_to_the_whole_run(engine, cfg):
     """Multi-GPU readiness without the node: the REAL engine on reads [0, N) against the REAL engine on the shards
