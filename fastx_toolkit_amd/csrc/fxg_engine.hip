@@ -4,6 +4,7 @@
 #include "fxg_history.h"
 #include "fxg_stats.h"
 #include "fxg_fallback.h"
+#include "fxg_barcode.h"
 
 extern "C" int fxg_abi_version(void) { return FXG_ABI_VERSION; }
 
@@ -44,6 +45,7 @@ extern "C" void fxg_ctx_destroy(fxg_ctx *c)
     (void)hipFree(c->status); (void)hipFree(c->errflag); (void)hipFree(c->counters_scratch);
     (void)hipFree(c->text_ws); (void)hipFree(c->text_state); (void)hipFree(c->fb_blk);
     (void)hipFree(c->hist_buf[0]); (void)hipFree(c->hist_buf[1]); (void)hipFree(c->hist_w); (void)hipFree(c->hist_ws); (void)hipFree(c->stats_ws); (void)hipFree(c->clip_ck);
+    (void)hipFree(c->bc_tab); (void)hipFree(c->bc_ws);
     (void)hipEventDestroy(c->ev0); (void)hipEventDestroy(c->ev1);
     for (int i = 0; i < FXG_KEV_RING; ++i) { if (c->kev0[i]) (void)hipEventDestroy(c->kev0[i]); if (c->kev1[i]) (void)hipEventDestroy(c->kev1[i]); }
     (void)hipStreamDestroy(c->own_stream);
@@ -604,6 +606,93 @@ extern "C" int fxg_fasta_weights(fxg_ctx *c, const uint8_t *d_text, const uint32
     hipLaunchKernelGGL(fxg_kernel_text_weights, dim3((u32)((n + FXG_BLOCK - 1) / FXG_BLOCK)), dim3(FXG_BLOCK), 0, c->stream, d_text, d_line, d_line + cap_lines, d_res, (u64)n, c->text_state);
     FXG_HIP(c, hipGetLastError());
     FXG_HIP(c, hipMemcpyAsync(weighted, c->text_state->weighted, 8 * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+    FXG_HIP(c, hipStreamSynchronize(c->stream));
+    return FXG_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// fastx_barcode_splitter (fxg_barcode.h): classify, scan, scatter
+// ------------------------------------------------------------------------------------------------
+extern "C" int fxg_barcode_prepare(fxg_ctx *c, const fxg_barcode_set *set)
+{
+    if (!c || !set) return FXG_E_INVALID;
+    c->bc_ready = 0;
+    const u32 E = set->entries, BL = set->barcode_len;
+    if (set->bins < 1 || set->bins > FXG_MAX_BARCODE_BINS) return fxg_fail(c, FXG_E_INVALID, "barcode split: %u bins (1 .. %d)", set->bins, FXG_MAX_BARCODE_BINS);
+    if (BL > FXG_MAX_BARCODE || (E > 0 && BL == 0)) return fxg_fail(c, FXG_E_INVALID, "barcode length %u (1 .. %d)", BL, FXG_MAX_BARCODE);
+    if (E > 0 && (!set->bases || !set->len || !set->bin)) return fxg_fail(c, FXG_E_INVALID, "barcode table without bases / lengths / bins");
+    FxgBcEntry *tab = (FxgBcEntry *)calloc(E ? E : 1, sizeof(FxgBcEntry));
+    if (!tab) return FXG_E_NOMEM;
+    for (u32 k = 0; k < E; ++k) {
+        const u32 L = set->len[k];
+        if (L > BL || set->bin[k] >= set->bins) { free(tab); return fxg_fail(c, FXG_E_INVALID, "barcode entry %u: length %u, bin %u", k, L, set->bin[k]); }
+        if (!fxg_bc_encode_entry(set->bases + (size_t)k * FXG_MAX_BARCODE, L, BL, set->bin[k], tab[k])) {
+            free(tab);
+            return fxg_fail(c, FXG_E_INVALID, "barcode entry %u: a base that is not A, C, G or T", k);
+        }
+    }
+    int rc = FXG_OK;
+    if (hipSetDevice(c->device) != hipSuccess) rc = fxg_fail(c, FXG_E_HIP, "hipSetDevice failed");
+    if (rc == FXG_OK && c->bc_tab_cap < (size_t)(E ? E : 1)) {
+        (void)hipFree(c->bc_tab);
+        c->bc_tab = nullptr; c->bc_tab_cap = 0;
+        if (hipMalloc((void **)&c->bc_tab, (size_t)(E ? E : 1) * sizeof(FxgBcEntry)) != hipSuccess) rc = fxg_fail(c, FXG_E_HIP, "hipMalloc of the barcode table failed");
+        else c->bc_tab_cap = E ? E : 1;
+    }
+    if (rc == FXG_OK && E > 0 && (hipMemcpyAsync(c->bc_tab, tab, (size_t)E * sizeof(FxgBcEntry), hipMemcpyHostToDevice, c->stream) != hipSuccess ||
+                                  hipStreamSynchronize(c->stream) != hipSuccess))
+        rc = fxg_fail(c, FXG_E_HIP, "upload of the barcode table failed");
+    free(tab);
+    if (rc != FXG_OK) return rc;
+    c->bc_entries = E; c->bc_len = BL; c->bc_mm = set->mismatches; c->bc_eol = set->eol ? 1u : 0u; c->bc_bins = set->bins;
+    c->bc_ready = 1;
+    return FXG_OK;
+}
+
+extern "C" int fxg_barcode_split(fxg_ctx *c, const uint8_t *d_text, uint64_t text_len, int lines_per_record, const uint32_t *d_line, uint64_t cap_lines,
+                                 uint64_t n, uint16_t *d_rec_bin, uint8_t *d_out, uint64_t *bin_bytes, uint64_t *bin_records)
+{
+    if (!c || !d_text || !d_line || !bin_bytes || !bin_records || (lines_per_record != 4 && lines_per_record != 2)) return FXG_E_INVALID;
+    if (!c->bc_ready) return fxg_fail(c, FXG_E_INVALID, "fxg_barcode_split: no table (fxg_barcode_prepare)");
+    const u32 bins = c->bc_bins;
+    memset(bin_bytes, 0, bins * sizeof(uint64_t));
+    memset(bin_records, 0, bins * sizeof(uint64_t));
+    if (n == 0) return FXG_OK;
+    if (!d_out) return FXG_E_INVALID;
+    if (((uintptr_t)d_text & 3u) != 0) return fxg_fail(c, FXG_E_INVALID, "fxg_barcode_split: the text must be 4-byte aligned");
+    if (text_len > 0xFFFFFFF0ull) return fxg_fail(c, FXG_E_INVALID, "text block too large (%llu bytes)", (unsigned long long)text_len);
+    if ((u64)lines_per_record * n + 1 > cap_lines) return fxg_fail(c, FXG_E_INVALID, "fxg_barcode_split: %llu records need more than %llu lines",
+                                                                   (unsigned long long)n, (unsigned long long)cap_lines);
+    FXG_HIP(c, hipSetDevice(c->device));
+    const u64 tiles = (n + FXG_BC_TILE - 1) / FXG_BC_TILE;
+    if (tiles > 0xFFFFFFFFull) return fxg_fail(c, FXG_E_INVALID, "fxg_barcode_split: too many records");
+    const u64 N = (u64)bins * tiles;
+    const u64 levels = N / 512 + 64;                         // fxg_scan_u64's block sums: N / 1024 + N / 1024^2 + ... + 8 per level
+    const u64 words = N + levels + 2 * (u64)bins + (d_rec_bin ? 0 : (n + 3) / 4);
+    if (c->bc_ws_cap < words) {
+        (void)hipFree(c->bc_ws);
+        c->bc_ws = nullptr; c->bc_ws_cap = 0;
+        const size_t cap = words + words / 4 + 4096;
+        FXG_HIP(c, hipMalloc((void **)&c->bc_ws, cap * sizeof(u64)));
+        c->bc_ws_cap = cap;
+    }
+    FxgBcArgs a;
+    a.text = d_text; a.ls = d_line; a.n = n; a.lpr = (u32)lines_per_record; a.tiles = (u32)tiles;
+    a.tab = c->bc_tab; a.entries = c->bc_entries; a.BL = c->bc_len; a.mismatches = c->bc_mm; a.eol = c->bc_eol; a.bins = bins;
+    a.hist_bytes = c->bc_ws;
+    u64 *tmp = c->bc_ws + N;
+    a.totals = tmp + levels;
+    a.rec_bin = d_rec_bin ? d_rec_bin : (uint16_t *)(a.totals + 2 * bins);
+    a.out = d_out;
+    FXG_HIP(c, hipMemsetAsync(a.totals, 0, 2 * bins * sizeof(u64), c->stream));
+    hipLaunchKernelGGL(fxg_kernel_bc_classify, dim3((u32)tiles), dim3(FXG_BC_TILE), 2 * bins * sizeof(u32), c->stream, a);
+    FXG_HIP(c, hipGetLastError());
+    const int rc = fxg_scan_u64(c, a.hist_bytes, N, tmp);
+    if (rc != FXG_OK) return rc;
+    hipLaunchKernelGGL(fxg_kernel_bc_scatter, dim3((u32)tiles), dim3(FXG_BC_TILE), 0, c->stream, a);
+    FXG_HIP(c, hipGetLastError());
+    FXG_HIP(c, hipMemcpyAsync(bin_bytes, a.totals, bins * sizeof(u64), hipMemcpyDeviceToHost, c->stream));
+    FXG_HIP(c, hipMemcpyAsync(bin_records, a.totals + bins, bins * sizeof(u64), hipMemcpyDeviceToHost, c->stream));
     FXG_HIP(c, hipStreamSynchronize(c->stream));
     return FXG_OK;
 }

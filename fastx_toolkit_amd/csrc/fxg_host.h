@@ -69,6 +69,13 @@ struct fxg_ctx {
     u64 *fb_blk; size_t fb_blk_cap;     // block sums / prefixes of the fallback
     int recoveries;                     // launches redone that way since the context was made (fxg_scan_recoveries)
     int test_force_timeout;             // FXG_TEST_SCAN_TIMEOUT=1: every compacting launch starts with the time-out flag up (GPU tier)
+    // barcode splitter (fxg_barcode_prepare / _split): the encoded table and the workspace of the per-(bin, tile) counts
+    struct FxgBcEntry *bc_tab;
+    size_t bc_tab_cap;                  // in entries
+    u32 bc_entries, bc_len, bc_mm, bc_eol, bc_bins;
+    int bc_ready;
+    u64 *bc_ws;
+    size_t bc_ws_cap;                   // in u64 words
 };
 
 static int fxg_fail(fxg_ctx *ctx, int code, const char *fmt, ...) __attribute__((unused));

@@ -26,6 +26,7 @@ EXPORTS = [
     "fxg_last_launch_info", "fxg_set_profiling", "fxg_last_kernel_ms", "fxg_profiled_kernel_ms", "fxg_set_clip_history", "fxg_run_quality_stats",
     "fxg_fastq_index", "fxg_fastq_pack", "fxg_fastq_format", "fxg_fasta_weights", "fxg_host_register", "fxg_host_unregister",
     "fxg_shard_range", "fxg_epilogue", "fxg_concat_pwrite", "fxg_concat_peer", "fxg_device_count", "fxg_device_numa_node", "fxg_comm_create", "fxg_comm_destroy", "fxg_epilogue_rccl",
+    "fxg_barcode_prepare", "fxg_barcode_split",
 ]
 
 
@@ -50,6 +51,15 @@ class FxgTextInfo(C.Structure):
     _fields_ = [("lines", C.c_uint64), ("records", C.c_uint64), ("consumed", C.c_uint64), ("max_len", C.c_uint32),
                 ("min_len", C.c_uint32), ("irregular", C.c_uint32), ("first_bad", C.c_uint32), ("numeric_records", C.c_uint32),
                 ("has_cr", C.c_uint32)]
+
+
+MAX_BARCODE = 64               # FXG_MAX_BARCODE
+MAX_BARCODE_BINS = 4096       # FXG_MAX_BARCODE_BINS
+
+
+class FxgBarcodeSet(C.Structure):
+    _fields_ = [("bases", C.c_void_p), ("len", C.c_void_p), ("bin", C.c_void_p), ("entries", C.c_uint32), ("barcode_len", C.c_uint32),
+                ("mismatches", C.c_uint32), ("eol", C.c_uint32), ("bins", C.c_uint32)]
 
 
 class FxgOut(C.Structure):
@@ -137,6 +147,8 @@ def load_library(path=None):
     L.fxg_comm_create.argtypes = [vp, C.c_char_p, u32, u32, i32, C.POINTER(vp)]
     L.fxg_comm_destroy.argtypes = [vp]; L.fxg_comm_destroy.restype = None
     L.fxg_epilogue_rccl.argtypes = [vp, vp, vp, vp, C.POINTER(u64), C.POINTER(u64), vp]
+    L.fxg_barcode_prepare.argtypes = [vp, C.POINTER(FxgBarcodeSet)]
+    L.fxg_barcode_split.argtypes = [vp, vp, u64, i32, vp, u64, u64, vp, vp, C.POINTER(u64), C.POINTER(u64)]
     L.fxg_set_profiling.argtypes = [vp, i32]
     L.fxg_set_clip_history.argtypes = [vp, i32]
     L.fxg_run_quality_stats.argtypes = [vp, C.POINTER(FxgBatch), vp, C.c_uint32]
@@ -436,6 +448,38 @@ class Engine:
         self._after_torch()
         self._check(self.lib.fxg_fasta_weights(self.ctx, d_text.data_ptr(), ix.line.data_ptr(), ix.cap_lines, n, res.data_ptr(), C.byref(w)))
         return list(w)
+
+    def barcode_prepare(self, entries, barcode_len, bins, mismatches=1, eol=False):
+        """Upload a barcode table: entries = [(bases, bin), ...] in table order (bases: bytes of A/C/G/T, at most barcode_len of them),
+        bins counting `unmatched`, which is bin bins - 1."""
+        E = len(entries)
+        bases = np.zeros((max(E, 1), MAX_BARCODE), dtype=np.uint8)
+        lens = np.zeros(max(E, 1), dtype=np.uint32)
+        bin_ = np.zeros(max(E, 1), dtype=np.uint32)
+        for k, (b, j) in enumerate(entries):
+            b = b.encode() if isinstance(b, str) else bytes(b)
+            if len(b) > MAX_BARCODE:
+                raise FxgError("barcode entry %d longer than %d bases" % (k, MAX_BARCODE))
+            bases[k, :len(b)] = np.frombuffer(b, dtype=np.uint8)
+            lens[k], bin_[k] = len(b), j
+        st = FxgBarcodeSet(bases.ctypes.data, lens.ctypes.data, bin_.ctypes.data, E, barcode_len, mismatches, int(bool(eol)), bins)
+        self._check(self.lib.fxg_barcode_prepare(self.ctx, C.byref(st)))
+        self._bc_bins = bins
+
+    def barcode_split(self, d_text, text_len, ix, n, out=None, rec_bin=True):
+        """Partition the n records of an indexed block (fastq_index) by the table of barcode_prepare.  Returns (out, bin_bytes, bin_records,
+        rec_bin): out holds bin 0's records, then bin 1's, ... (a view of exactly their bytes); rec_bin (int16 tensor) or None."""
+        bins = self._bc_bins
+        starts = ix.starts
+        nbytes = int(starts[ix.lpr * n].item()) - int(starts[0].item()) if n else 0
+        if out is None:
+            out = self.torch.empty(max(nbytes, 1), dtype=self.torch.uint8, device=self.device)
+        rb = self.torch.empty(max(n, 1), dtype=self.torch.int16, device=self.device) if rec_bin else None
+        bb, br = (C.c_uint64 * bins)(), (C.c_uint64 * bins)()
+        self._after_torch()
+        self._check(self.lib.fxg_barcode_split(self.ctx, d_text.data_ptr(), text_len, ix.lpr, ix.line.data_ptr(), ix.cap_lines, n,
+                                               rb.data_ptr() if rb is not None else None, out.data_ptr(), bb, br))
+        return out[:nbytes], np.array(list(bb), dtype=np.uint64), np.array(list(br), dtype=np.uint64), (rb[:n] if rb is not None else None)
 
     def read_counters(self, d_counters):
         host = (C.c_uint64 * NCOUNTERS)()

@@ -181,6 +181,9 @@ typedef struct fxg_out {
  *   text path (below)        d_text: read text_len + 16 bytes (the 16 are slack: their values never matter); d_line: 2 * cap_lines uint32;
  *                            d_len, d_flags: cap_lines / lines_per_record entries; packed rows: records * stride rounded up to 16 bytes (whole
  *                            16-byte chunks are written); d_out: text_len + records + 16 bytes; d_res, d_pk_*: records entries / the packed stream.
+ *   barcode split (below)    d_text: read as for the text path; d_line: the line starts ls[0 .. lines_per_record * records] (first half only);
+ *                            d_rec_bin: write records uint16; d_out: write exactly ls[lines_per_record * records] - ls[0] bytes (the records
+ *                            themselves), never a byte past them.
  * tests/test_emu_bounds.py runs the kernels' bodies with every array against a guard page at these ends; tests/test_gpu_bounds.py surrounds every
  * array with poison (inputs) and canaries (outputs) on the device. */
 
@@ -282,6 +285,32 @@ int  fxg_fastq_format(fxg_ctx *ctx, const uint8_t *d_text, int lines_per_record,
  * weighted tallies over the block: input, kept, clip too-short, adapter-only, no-adapter, adapter-found, has-N. */
 int  fxg_fasta_weights(fxg_ctx *ctx, const uint8_t *d_text, const uint32_t *d_line, uint64_t cap_lines, uint64_t records, const uint32_t *d_res,
                        uint64_t weighted[8]);
+/* fastx_barcode_splitter (reference scripts/fastx_barcode_splitter.pl): a stable partition of a block's records into `bins` bins by their
+ * barcode.  The table holds `entries` entries in the script's order (a barcode, then its --partial shortenings): entry e's bases are
+ * bases[e * FXG_MAX_BARCODE ...], upper-case A/C/G/T, len[e] <= barcode_len of them, and it names bin[e] < bins.  Bin bins - 1 is
+ * `unmatched` (an entry may name it too).  A record's window is the first (eol == 0) or last min(barcode_len, bases) bytes of its bases line
+ * without the '\n'; an entry's mismatches are the window's length minus the bytes equal to the entry's minus the NUL bytes past the entry's
+ * end, plus barcode_len - len[e].  The record goes to the first entry with the fewest mismatches, if those are below barcode_len and at most
+ * `mismatches`; to bin bins - 1 otherwise.  Every byte of the window is compared as it is (CR, NUL, lower case). */
+#define FXG_MAX_BARCODE 64
+#define FXG_MAX_BARCODE_BINS 4096
+typedef struct fxg_barcode_set {
+    const uint8_t  *bases;        /* host, entries * FXG_MAX_BARCODE bytes */
+    const uint32_t *len;          /* host, entries */
+    const uint32_t *bin;          /* host, entries */
+    uint32_t entries;             /* any number, 0 included (then every record is unmatched) */
+    uint32_t barcode_len;         /* 1 .. FXG_MAX_BARCODE (0 only without entries) */
+    uint32_t mismatches;
+    uint32_t eol;                 /* 0: --bol, 1: --eol */
+    uint32_t bins;                /* 1 .. FXG_MAX_BARCODE_BINS, unmatched included */
+} fxg_barcode_set;
+/* Encodes the table and uploads it; it serves every fxg_barcode_split on this context until the next prepare. */
+int  fxg_barcode_prepare(fxg_ctx *ctx, const fxg_barcode_set *set);
+/* Splits the `records` complete records of a block indexed by fxg_fastq_index (d_line, cap_lines as given to it; d_text 4-byte aligned).
+ * d_out receives bin 0's records, then bin 1's, ..., each bin's in input order and as their input bytes; bin_bytes[b] / bin_records[b]
+ * (host, bins entries each) say how many.  d_rec_bin (optional): the bin of every record.  Synchronises. */
+int  fxg_barcode_split(fxg_ctx *ctx, const uint8_t *d_text, uint64_t text_len, int lines_per_record, const uint32_t *d_line, uint64_t cap_lines,
+                       uint64_t records, uint16_t *d_rec_bin, uint8_t *d_out, uint64_t *bin_bytes, uint64_t *bin_records);
 int  fxg_host_register(fxg_ctx *ctx, void *ptr, size_t bytes);     /* page-lock an existing host buffer for async copies */
 int  fxg_host_unregister(fxg_ctx *ctx, void *ptr);
 
