@@ -28,10 +28,6 @@ typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 #define FXG_TBLOCK 256          // threads per workgroup of the tile kernels
 #endif
 #define FXG_TWAVES (FXG_TBLOCK / 64)
-#ifndef FXG_STORE_GRID
-#define FXG_STORE_GRID 1            // fxg_rows_flush deals its 16-byte units to lanes by the unit's place in its 128-byte line (0: by the unit's place in the tile's output; the A/B arm).
-                                    // The tile kernels' gather was measured the same way and lost 1.6-3 % (cfg4, cfg3, cfg5: profiles/r06/store_grid_other.txt): it keeps chunk ci on lane ci.
-#endif
 #ifndef FXG_CLIP_GATHER_K
 #define FXG_CLIP_GATHER_K 4     // chunks per lane in flight in the clip instances' gather (FXG_GATHER_K for the streaming instances)
 #endif
@@ -90,7 +86,7 @@ struct FxgKArgs {
     int  qf_keep_pct;       // 100 - p
     u32  qf_drop_all;       // quirk F2: -p omitted and -q > 93
     int  alen;
-    u32  adapter_has_n;     // the adapter contains 'N' (the clip kernels then keep the per-column neutral-match selects)
+    u32  adapter_has_n;     // the adapter contains 'N'.  Read by no kernel (an 'N' is one more column pattern of the pair table); kept for the argument layout
     u32  clip_min_len;
     int  clip_keep_delta;
     int  clip_min_adapter_len;
@@ -112,9 +108,6 @@ struct FxgKArgs {
     u32  clip_ptab_stride;  // bytes between two of its rows (an odd multiple of 16 where rows are wider than a bank sweep: fxg_ptab_stride)
     u32  clip_ptab_cols;    // columns per row (the instance's bucket rounded up to a multiple of four)
     u32  clip_ptab_dia1;    // what a non-neutral diagonal step adds to the path summary of the instance's form (FXG_PK_DIA1 / FXG_K_DIA1)
-#ifdef FXG_CLIP_DEBUG
-    u32 *clip_dbg;          // debug builds only (scripts/debug/clip64_bisect.py): 16 words per read of fxg_clip_two_pass_k's intermediate state
-#endif
     char adapter[100];
     uint8_t clip_ptab_row[256];   // pair table: row of every byte value (fxg_plan.h fills it: 0 = not in the adapter, 1 = 'N', 2.. = the adapter's distinct bytes in order of first appearance); bit 7 = this byte's thread writes the row
 };
@@ -172,19 +165,12 @@ FXG_HD u32x4 fxg_ld16(const uint8_t *p)
 }
 // Streaming forms for data touched exactly once by the gather.  Measured on cfg2 / cfg4: `nt` on the packed-output stores
 // is worth 4 % / -2 %; `nt` on the source windows costs 4 % / 7 % (neighbouring lanes' unaligned windows share lines), so
-// the loads stay plain unless FXG_V_NTL is defined.
+// the loads stay plain.
 typedef u32x4 u32x4_unaligned __attribute__((aligned(1)));
-FXG_HD u32x4 fxg_ld16_stream(const uint8_t *p)
-{
-#if defined(FXG_V_NTL) && !defined(FXG_HOST_EMULATION)
-    return __builtin_nontemporal_load(reinterpret_cast<const u32x4_unaligned *>(p));
-#else
-    return fxg_ld16(p);
-#endif
-}
+FXG_HD u32x4 fxg_ld16_stream(const uint8_t *p) { return fxg_ld16(p); }
 FXG_HD void fxg_st16_stream(uint8_t *p, u32x4 v)
 {
-#if !defined(FXG_V_NO_NTS) && !defined(FXG_HOST_EMULATION)
+#ifndef FXG_HOST_EMULATION
     __builtin_nontemporal_store(v, reinterpret_cast<u32x4 *>(p));
 #else
     *reinterpret_cast<u32x4 *>(p) = v;
@@ -616,9 +602,7 @@ FXG_HD u32 fxg_rank_of(const u32 *k_off, const uint16_t *k_tab, u32 nk, u32 S, u
         const u32 g = o >> 4;
         lo = k_tab[g];
         hi = ((g + 1u) << 4) < S ? (u32)k_tab[g + 1u] + 1u : nk;
-    }
-#ifndef FXG_NO_RANK_GUESS
-    else if (nk > 8u) {
+    } else if (nk > 8u) {
         // No granule table (the clip instances: their LDS holds a tile of bases): start from where the byte would be if all kept reads had the tile's mean
         // length and bracket it with steps of 1, 2, 4, ... -- kept lengths are close to one another, so the bracket is a few reads wide instead of the whole
         // tile and the bisection below takes 1-3 dependent LDS reads instead of 8 (round 6).
@@ -636,7 +620,6 @@ FXG_HD u32 fxg_rank_of(const u32 *k_off, const uint16_t *k_tab, u32 nk, u32 S, u
             while (k_off[lo] > o) { hi = lo; step <<= 1; lo = lo > step ? lo - step : 0u; }
         }
     }
-#endif
     while (hi - lo > 1u) {
         const u32 mid = (lo + hi) >> 1;
         if (k_off[mid] <= o) lo = mid; else hi = mid;

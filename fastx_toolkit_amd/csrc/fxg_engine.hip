@@ -252,7 +252,7 @@ static int fxg_launch_plan(fxg_ctx *c, FxgPlan &pl, u64 *ctr)
     if (pl.group_a) {
         if (pl.amax == 0) return fxg_launch_tiles(c, FXG_TILES_A(0), "fxg_kernel_tiles<0,0> qtrim+qfilter", pl.ka, pl.lds, ctr);
         // the clipper's instances live in translation units of their own (fxg_engine_clip.hip)
-        return pl.amax <= -300 ? fxg_launch_clip_n(c, pl, ctr) : (pl.amax < -16 && pl.amax > -200) ? fxg_launch_clip_k(c, pl, ctr) : fxg_launch_clip_reg(c, pl, ctr);
+        return pl.amax < -16 ? fxg_launch_clip_k(c, pl, ctr) : fxg_launch_clip_reg(c, pl, ctr);
     }
     if (pl.mask) return fxg_launch_tiles(c, fxg_kernel_tiles<0, 3>, "fxg_kernel_tiles<0,3> mask", pl.ka, pl.lds, ctr);
     if (pl.artifacts) return fxg_launch_tiles(c, fxg_kernel_tiles<0, 4>, "fxg_kernel_tiles<0,4> base census", pl.ka, pl.lds, ctr);
@@ -782,7 +782,7 @@ extern "C" int fxg_set_profiling(fxg_ctx *c, int enabled)
     return FXG_OK;
 }
 
-#if defined(FXG_ABLATION) || defined(FXG_ABL_ROWCLK)
+#ifdef FXG_ABLATION
 // timing experiments only (scripts/ablate.py): the phase clocks fxg_kernel_rows adds up in the control block, words 10..
 extern "C" int fxg_debug_phase_clocks(fxg_ctx *c, uint64_t out[11])
 {

@@ -1,12 +1,13 @@
-// fxg_engine_clip.hip -- the clip instances of fxg_kernel_tiles, in three groups so that they can be compiled side by side (fxg_host.h).
-// -DFXG_CLIP_TU=1 .. 7 compiles one group; without it (included by fxg_engine.hip in a single-unit build) all of them.
+// fxg_engine_clip.hip -- the clip instances of fxg_kernel_tiles, in seven groups so that they can be compiled side by side (fxg_host.h).
+// -DFXG_CLIP_TU=1 .. 7 compiles one group; without it (included by fxg_engine.hip in a single-unit build) all of them.  A launch that no
+// group's switch takes goes on to the next group's, in the order 1, 2, 4, 6, 3, 5, 7.
 #include "fxg_host.h"
 
 #define FXG_TILES_A(N) (fxg_kernel_tiles<N, 0>)
 #define FXG_TILES_C(N) (pl.ka.clip_global ? fxg_kernel_tiles<N, 0, true> : fxg_kernel_tiles<N, 0, false>)      // packed clip instances: the DP over the staged tile, or over the batch (fxg_plan.h)
 
 #if !defined(FXG_CLIP_TU) || FXG_CLIP_TU == 1
-// adapters of up to 16 bases without N: two passes in registers; and the general two-word form (positive codes: FXG_NO_PACKED_CLIP, one-pass corner cases)
+// adapters of up to 16 bases: two passes in registers; and the general two-word form (positive codes: FXG_NO_PACKED_CLIP, one-pass corner cases)
 int fxg_launch_clip_reg(fxg_ctx *c, FxgPlan &pl, u64 *ctr)
 {
     switch (pl.amax) {
@@ -20,9 +21,6 @@ int fxg_launch_clip_reg(fxg_ctx *c, FxgPlan &pl, u64 *ctr)
         case -14: return fxg_launch_tiles(c, FXG_TILES_C(-14), "fxg_kernel_tiles<-14,0> clip(packed)[+qtrim+qfilter]", pl.ka, pl.lds, ctr, pl.block);
         case -15: return fxg_launch_tiles(c, FXG_TILES_C(-15), "fxg_kernel_tiles<-15,0> clip(packed)[+qtrim+qfilter]", pl.ka, pl.lds, ctr, pl.block);
         case -16: return fxg_launch_tiles(c, FXG_TILES_C(-16), "fxg_kernel_tiles<-16,0> clip(packed)[+qtrim+qfilter]", pl.ka, pl.lds, ctr, pl.block);
-#ifdef FXG_CLIP_ONE_PASS     // (ablation build only: reads beyond 255 bases with a short adapter; the regular build's register form takes them)
-        case -216: return fxg_launch_tiles(c, FXG_TILES_C(-216), "fxg_kernel_tiles<-216,0> clip(packed)[+qtrim+qfilter]", pl.ka, pl.lds, ctr, FXG_TBLOCK, false, pl.ck_per_wg);
-#endif
         case 16: return fxg_launch_tiles(c, FXG_TILES_A(16), "fxg_kernel_tiles<16,0> clip[+qtrim+qfilter]", pl.ka, pl.lds, ctr);
         case 32: return fxg_launch_tiles(c, FXG_TILES_A(32), "fxg_kernel_tiles<32,0> clip[+qtrim+qfilter]", pl.ka, pl.lds, ctr);
         case 64: return fxg_launch_tiles(c, FXG_TILES_A(64), "fxg_kernel_tiles<64,0> clip[+qtrim+qfilter]", pl.ka, pl.lds, ctr);
@@ -67,63 +65,22 @@ int fxg_launch_clip_k_wide_wide(fxg_ctx *c, FxgPlan &pl, u64 *ctr)
         case -64: return fxg_launch_tiles(c, FXG_TILES_C(-64), "fxg_kernel_tiles<-64,0> clip(packed)[+qtrim+qfilter]", pl.ka, pl.lds, ctr, FXG_TBLOCK, false, pl.ck_per_wg);
         case -80: return fxg_launch_tiles(c, FXG_TILES_C(-80), "fxg_kernel_tiles<-80,0> clip(packed)[+qtrim+qfilter]", pl.ka, pl.lds, ctr, FXG_TBLOCK, false, pl.ck_per_wg);
         case -100: return fxg_launch_tiles(c, FXG_TILES_C(-100), "fxg_kernel_tiles<-100,0> clip(packed)[+qtrim+qfilter]", pl.ka, pl.lds, ctr, FXG_TBLOCK, false, pl.ck_per_wg);
-    default: return fxg_launch_clip_n(c, pl, ctr);      // (the buckets of round 6 live in the translation units the N instances left: below)
+    default: return fxg_launch_clip_k44_52(c, pl, ctr);      // (the buckets of round 6: below)
     }
 }
 #endif
 
-// adapters that contain N: instances of their own only in builds without the pair table (-DFXG_NO_PTAB: A/B measurements); with it an N is one more column
-// pattern of the table and the plan never asks for them (fxg_plan.h)
-#ifndef FXG_NO_PTAB
+// 44 / 52, 60 / 72 and 88 columns (the buckets of round 6), one translation unit each
 #define FXG_K(N) case -N: return fxg_launch_tiles(c, FXG_TILES_C(-N), "fxg_kernel_tiles<-" #N ",0> clip(packed)[+qtrim+qfilter]", pl.ka, pl.lds, ctr, FXG_TBLOCK, false, pl.ck_per_wg)
 #if !defined(FXG_CLIP_TU) || FXG_CLIP_TU == 3
-int fxg_launch_clip_n(fxg_ctx *c, FxgPlan &pl, u64 *ctr) { switch (pl.amax) { FXG_K(44); FXG_K(52); default: return fxg_launch_clip_n_wide(c, pl, ctr); } }
+int fxg_launch_clip_k44_52(fxg_ctx *c, FxgPlan &pl, u64 *ctr) { switch (pl.amax) { FXG_K(44); FXG_K(52); default: return fxg_launch_clip_k60_72(c, pl, ctr); } }
 #endif
 #if !defined(FXG_CLIP_TU) || FXG_CLIP_TU == 5
-int fxg_launch_clip_n_wide(fxg_ctx *c, FxgPlan &pl, u64 *ctr) { switch (pl.amax) { FXG_K(60); FXG_K(72); default: return fxg_launch_clip_n_wide_wide(c, pl, ctr); } }
+int fxg_launch_clip_k60_72(fxg_ctx *c, FxgPlan &pl, u64 *ctr) { switch (pl.amax) { FXG_K(60); FXG_K(72); default: return fxg_launch_clip_k88(c, pl, ctr); } }
 #endif
 #if !defined(FXG_CLIP_TU) || FXG_CLIP_TU == 7
-int fxg_launch_clip_n_wide_wide(fxg_ctx *c, FxgPlan &pl, u64 *ctr) { switch (pl.amax) { FXG_K(88); default: return fxg_fail(c, FXG_E_INVALID, "no clip instance %d", pl.amax); } }
+int fxg_launch_clip_k88(fxg_ctx *c, FxgPlan &pl, u64 *ctr) { switch (pl.amax) { FXG_K(88); default: return fxg_fail(c, FXG_E_INVALID, "no clip instance %d", pl.amax); } }
 #endif
 #undef FXG_K
-#else
-#if !defined(FXG_CLIP_TU) || FXG_CLIP_TU == 3
-// adapters that contain N
-int fxg_launch_clip_n(fxg_ctx *c, FxgPlan &pl, u64 *ctr)
-{
-    switch (pl.amax) {
-        case -316: return fxg_launch_tiles(c, FXG_TILES_C(-316), "fxg_kernel_tiles<-316,0> clip(packed, N in the adapter)[+qtrim+qfilter]", pl.ka, pl.lds, ctr, FXG_TBLOCK, false, pl.ck_per_wg);
-        case -324: return fxg_launch_tiles(c, FXG_TILES_C(-324), "fxg_kernel_tiles<-324,0> clip(packed, N in the adapter)[+qtrim+qfilter]", pl.ka, pl.lds, ctr, FXG_TBLOCK, false, pl.ck_per_wg);
-        case -336: return fxg_launch_tiles(c, FXG_TILES_C(-336), "fxg_kernel_tiles<-336,0> clip(packed, N in the adapter)[+qtrim+qfilter]", pl.ka, pl.lds, ctr, FXG_TBLOCK, false, pl.ck_per_wg);
-    default: return fxg_launch_clip_n_wide(c, pl, ctr);
-    }
-}
-#endif
-
-#if !defined(FXG_CLIP_TU) || FXG_CLIP_TU == 5
-// ... of more than 36 columns
-int fxg_launch_clip_n_wide(fxg_ctx *c, FxgPlan &pl, u64 *ctr)
-{
-    switch (pl.amax) {
-        case -348: return fxg_launch_tiles(c, FXG_TILES_C(-348), "fxg_kernel_tiles<-348,0> clip(packed, N in the adapter)[+qtrim+qfilter]", pl.ka, pl.lds, ctr, FXG_TBLOCK, false, pl.ck_per_wg);
-        case -356: return fxg_launch_tiles(c, FXG_TILES_C(-356), "fxg_kernel_tiles<-356,0> clip(packed, N in the adapter)[+qtrim+qfilter]", pl.ka, pl.lds, ctr, FXG_TBLOCK, false, pl.ck_per_wg);
-    default: return fxg_launch_clip_n_wide_wide(c, pl, ctr);
-    }
-}
-#endif
-
-#if !defined(FXG_CLIP_TU) || FXG_CLIP_TU == 7
-// ... 64, 80 and 100 columns
-int fxg_launch_clip_n_wide_wide(fxg_ctx *c, FxgPlan &pl, u64 *ctr)
-{
-    switch (pl.amax) {
-        case -364: return fxg_launch_tiles(c, FXG_TILES_C(-364), "fxg_kernel_tiles<-364,0> clip(packed, N in the adapter)[+qtrim+qfilter]", pl.ka, pl.lds, ctr, FXG_TBLOCK, false, pl.ck_per_wg);
-        case -380: return fxg_launch_tiles(c, FXG_TILES_C(-380), "fxg_kernel_tiles<-380,0> clip(packed, N in the adapter)[+qtrim+qfilter]", pl.ka, pl.lds, ctr, FXG_TBLOCK, false, pl.ck_per_wg);
-        case -400: return fxg_launch_tiles(c, FXG_TILES_C(-400), "fxg_kernel_tiles<-400,0> clip(packed, N in the adapter)[+qtrim+qfilter]", pl.ka, pl.lds, ctr, FXG_TBLOCK, false, pl.ck_per_wg);
-    default: return fxg_fail(c, FXG_E_INVALID, "no clip instance %d", pl.amax);
-    }
-}
-#endif
-#endif      // FXG_NO_PTAB
 #undef FXG_TILES_A
 #undef FXG_TILES_C

@@ -1,8 +1,8 @@
 // fxg_host.h -- what the translation units of the engine share on the host side: the context, the error macros, the launch of one instance of a tile
 // kernel.  The engine is built from EIGHT translation units compiled side by side (fastx_toolkit_amd/build.py): fxg_engine.hip (every entry point of the
 // C-ABI and every kernel but the clipper's) and fxg_engine_clip.hip seven times (-DFXG_CLIP_TU=1: the register forms of up to 16 columns and the general
-// form; 2 / 4 / 6: 17..36 / 40..56 / 64..100 columns; 3 / 5 / 7: the same for adapters that contain N) -- the 64 clip instances are most of what hipcc spends its time on, and one translation unit of
-// 100 kernels took three and a half minutes.  Compiled alone (no -DFXG_SPLIT: the variant / matrix / ablation builds of scripts/) fxg_engine.hip includes
+// form; 2 / 4 / 6: 20..36 / 40, 48, 56 / 64, 80, 100 columns; 3 / 5 / 7: 44, 52 / 60, 72 / 88 columns) -- the clip instances are most of what hipcc spends its
+// time on, and one translation unit of 100 kernels took three and a half minutes.  Compiled alone (no -DFXG_SPLIT: the variant / matrix / ablation builds of scripts/) fxg_engine.hip includes
 // the clip file and is the one translation unit it used to be.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -105,9 +105,9 @@ FXG_INTERNAL int fxg_launch_clip_reg(fxg_ctx *c, FxgPlan &pl, u64 *ctr);
 FXG_INTERNAL int fxg_launch_clip_k(fxg_ctx *c, FxgPlan &pl, u64 *ctr);
 FXG_INTERNAL int fxg_launch_clip_k_wide(fxg_ctx *c, FxgPlan &pl, u64 *ctr);
 FXG_INTERNAL int fxg_launch_clip_k_wide_wide(fxg_ctx *c, FxgPlan &pl, u64 *ctr);
-FXG_INTERNAL int fxg_launch_clip_n(fxg_ctx *c, FxgPlan &pl, u64 *ctr);
-FXG_INTERNAL int fxg_launch_clip_n_wide(fxg_ctx *c, FxgPlan &pl, u64 *ctr);
-FXG_INTERNAL int fxg_launch_clip_n_wide_wide(fxg_ctx *c, FxgPlan &pl, u64 *ctr);
+FXG_INTERNAL int fxg_launch_clip_k44_52(fxg_ctx *c, FxgPlan &pl, u64 *ctr);
+FXG_INTERNAL int fxg_launch_clip_k60_72(fxg_ctx *c, FxgPlan &pl, u64 *ctr);
+FXG_INTERNAL int fxg_launch_clip_k88(fxg_ctx *c, FxgPlan &pl, u64 *ctr);
 
 // ------------------------------------------------------------------------------------------------
 
@@ -191,15 +191,6 @@ static int fxg_launch_tiles(fxg_ctx *c, K kernel, const char *kname, FxgKArgs &k
 #if defined(FXG_ABLATION) || defined(FXG_DBG_BITS)
     { const char *dbg = getenv("FXG_DEBUG"); ka.debug = dbg ? (u32)atoi(dbg) : 0u; }
 #endif
-#ifdef FXG_CLIP_DEBUG   // debug builds only (scripts/debug/clip64_bisect.py): FXG_CLIP_DBG_WORDS words per read from fxg_clip_two_pass_k, appended to $FXG_CLIP_DEBUG_OUT
-    u32 *clip_dbg = nullptr;
-    ka.clip_dbg = nullptr;
-    if (ck_per_wg && getenv("FXG_CLIP_DEBUG_OUT")) {
-        FXG_HIP(c, hipMalloc((void **)&clip_dbg, (size_t)ka.n * FXG_CLIP_DBG_WORDS * 4));
-        FXG_HIP(c, hipMemsetAsync(clip_dbg, 0xEE, (size_t)ka.n * FXG_CLIP_DBG_WORDS * 4, c->stream));
-        ka.clip_dbg = clip_dbg;
-    }
-#endif
     ka.errflag = c->errflag;                     // control block (zeroed before every launch), layout at FXG_CTRL_WORDS
     ka.ticket = c->errflag + FXG_CTRL_WORDS;
     ka.extra = (u64 *)(c->errflag + 2);
@@ -225,16 +216,5 @@ static int fxg_launch_tiles(fxg_ctx *c, K kernel, const char *kname, FxgKArgs &k
     { const int frc2 = fxg_enqueue_finish_counters(c, ka, counters); if (frc2 != FXG_OK) return frc2; }      // -v report counters: the tile kernel tallied them; one tiny kernel lays them out
     snprintf(c->last_kernel, sizeof c->last_kernel, "%s", kname);
     c->last_grid = (u32)grid; c->last_block = block; c->last_lds = lds; c->last_tile = ka.tile_reads;
-#ifdef FXG_CLIP_DEBUG
-    if (clip_dbg) {
-        u32 *h = (u32 *)malloc((size_t)ka.n * FXG_CLIP_DBG_WORDS * 4);
-        FXG_HIP(c, hipStreamSynchronize(c->stream));
-        FXG_HIP(c, hipMemcpy(h, clip_dbg, (size_t)ka.n * FXG_CLIP_DBG_WORDS * 4, hipMemcpyDeviceToHost));
-        FILE *f = fopen(getenv("FXG_CLIP_DEBUG_OUT"), "ab");
-        if (f) { fwrite(h, FXG_CLIP_DBG_WORDS * 4, (size_t)ka.n, f); fclose(f); }
-        free(h);
-        (void)hipFree(clip_dbg);
-    }
-#endif
     return FXG_OK;
 }

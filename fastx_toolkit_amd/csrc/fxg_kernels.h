@@ -177,130 +177,12 @@ FXG_HD void fxg_clip_read(const FxgKArgs &a, const uint8_t *rd, int len, int row
 
 // Packed form for adapters up to 16 columns (every BASELINE config; the field widths would take 31): the whole path summary is ONE u32
 //   w = query_start:8 | target_start:5 | diagonal:5 | path_len:9 | matches:5      (path_len <= L + A <= 286)
-// `diagonal` counts the non-neutral diagonal steps (matches + mismatches): it grows by a constant of the row (0 when the read
-// base is 'N'), and `matches` sits in the lowest bits so that "+1 where read base == adapter base" is the carry-in of that
-// same addition (v_addc_co_u32): a diagonal step is ONE instruction.  mismatches = diagonal - matches at the end.
+// `diagonal` counts the non-neutral diagonal steps (matches + mismatches) and `matches` sits in the lowest bits, so that a diagonal step
+// adds ONE number: DIA1 + MAT1 where the bases are equal, DIA1 where they differ, 0 where either is 'N' (the step rows of the pair table,
+// fxg_clip_ptab_build).  mismatches = diagonal - matches at the end.
 #define FXG_PK_MAT1  1u
 #define FXG_PK_SZ1   (1u << 5)
 #define FXG_PK_DIA1  (1u << 14)
-// FIRST: row q == 0.  The "path enters the matrix here" test can only fire where a predecessor lies outside the matrix:
-// anywhere in row 0, and in column 0 of the other rows -- so rows q >= 1 test it at t == 0 only.
-// TN: the adapter may contain 'N'.  Without it the pair score of a cell is one select on "read base == adapter base" between
-// two values fixed per row (an 'N' in the read makes both 0.1 / neutral, and can never equal an adapter base).
-// W holds every cell's summary ALREADY extended by one gap step (w + SZ1): that is what both the cell below (up) and the cell to
-// the right in the next row (left) need, so the step is added once per cell instead of once per use; the diagonal adds the
-// difference.  "No predecessor" is the value 0, which no extended summary can be (its path_len is >= 2).
-// Sm holds every cell's score minus the gap penalty for the same reason (one subtraction serves `up` and `left`).
-// Cell rule (sequence_alignment.cpp:380-417): strict '>' from diag to up to left, i.e. the maximum with ties going to diag, then up:
-//   score = max3(ul, up, left); diag iff score == ul; else up iff score == up; else left.
-// TRACK = false: the row cannot hold the first maximum (the second pass of fxg_clip_two_pass knows its row) -- no best-cell update.
-// vstart: what a path that enters the matrix in this row records as its query_start (8 bits): the row itself in the one-pass form, the
-// row relative to the second pass' first row in fxg_clip_two_pass -- which is what lets that form take reads of any length.
-template <int AMAX, bool EARLY, bool FIRST, bool TN, bool TRACK = true>
-FXG_HD void fxg_clip_row_packed(const FxgKArgs &a, int A, u32 c, int q, u32 vstart, float (&S)[AMAX], float (&Sm)[AMAX], u32 (&W)[AMAX], float &best, u32 &bw, u32 &bq)
-{
-    const bool qn = (c == (u32)'N');
-    const float pair_eq = qn ? 0.1f : 1.0f, pair_ne = qn ? 0.1f : -1.0f;                 // sequence_alignment.h:157-169 for a target base that is not N
-    const u32 dxr = qn ? 0u : FXG_PK_DIA1;                                               // what a diagonal step adds besides a match
-    const float best_in = best;
-    // pass 1: everything a cell takes from the row above -- the diagonal candidates ul = S[q-1][t-1] + pair and their summaries.
-    // Done for the whole row first so that the old S / W values are dead before pass 2 overwrites them in place (no register
-    // rotation in the rolled row loop) and so that only the up/left chain is left on the dependent path.
-    float ul[AMAX];
-    u32 wd[AMAX], dWv[AMAX];
-#pragma unroll
-    for (int t = 0; t < AMAX; ++t) {
-        const u32 tc = (u32)(uint8_t)a.adapter[t];    // straight-line body, see fxg_clip_read
-        const bool eq = (c == tc);
-        float pair = eq ? pair_eq : pair_ne;
-        const float dS = t ? S[t - 1] : 0.0f;              // S[q-1][-1]: query_border = 0 (N1 for q == 0)
-        const u32 dW = t ? W[t - 1] : 0u;                  // no predecessor left of column 0
-        if (TN) {
-            const bool tn = (tc == (u32)'N');
-            pair = tn ? (qn ? 0.0f : 0.1f) : pair;
-            wd[t] = dW + (tn ? 0u : dxr + (eq ? FXG_PK_MAT1 : 0u));
-        } else {
-            wd[t] = (dW + dxr) + (u32)eq;
-        }
-        ul[t] = dS + pair;
-        dWv[t] = dW;
-    }
-    // pass 2: the chain along the row
-    float uSm = -5.0f;                                     // S[q][-1] - 5
-    u32 uW = 0u;
-#pragma unroll
-    for (int t = 0; t < AMAX; ++t) {
-        const float up = uSm;
-        float left = Sm[t];
-        if (EARLY && t > 3) left = (t - 3 > q) ? -100000.0f : left;                          // :387-389, only rows q < A-4
-        const float sc = fmaxf(fmaxf(ul[t], up), left);
-        const bool isd = (sc == ul[t]), isu = (sc == up);
-        u32 w;
-        if (FIRST || t == 0) {                                                               // a predecessor may lie outside the matrix
-            const u32 src = isd ? dWv[t] : (isu ? uW : W[t]);
-            const u32 step = isd ? wd[t] - dWv[t] : 0u;
-            w = (src == 0u) ? (((vstart << 24) | ((u32)t << 19)) + FXG_PK_SZ1 + step) : (src + step);   // the path enters the matrix here
-        } else {
-            w = isu ? uW : W[t];
-            w = isd ? wd[t] : w;
-        }
-        const u32 wp = w + FXG_PK_SZ1;
-        const float scm = sc + -5.0f;
-        S[t] = sc; Sm[t] = scm; W[t] = wp;
-        uSm = scm; uW = wp;
-        // first maximum in query-major order.  Columns past the adapter (t >= A) do not count; the smallest adapter of this
-        // bucket has AMIN bases, so only columns t >= AMIN need the test (none for the exact buckets 9..16) -- a mask that went
-        // through a scalar AND costs a v_cndmask several times what a mask straight from a v_cmp does (scripts/ubench/valu_rate.hip).
-        constexpr int AMIN = AMAX <= 4 ? 1 : (AMAX <= 8 ? 5 : (AMAX <= 16 ? AMAX : AMAX - 3));
-        if (!TRACK) continue;
-        if (t < AMIN) {
-            const bool gb = sc > best;
-            bw = gb ? w : bw;
-            best = fmaxf(best, sc);
-        } else {
-            const bool gb = (sc > best) && (t < A);
-            best = gb ? sc : best; bw = gb ? w : bw;
-        }
-    }
-    if (TRACK) bq = (best > best_in) ? (u32)q : bq;        // the best cell moved into this row (best only ever grows)
-}
-
-template <int AMAX, bool TN>
-FXG_HD void fxg_clip_rows_packed(const FxgKArgs &a, const uint8_t *rd, int len, int rows, float &best, u32 &bw, u32 &bq, int &first_n, const bool UR = false)
-{
-    float S[AMAX], Sm[AMAX];
-    u32 W[AMAX];
-    const int A = a.alen;
-#pragma unroll
-    for (int t = 0; t < AMAX; ++t) { S[t] = (t <= 3) ? 0.0f : -5.0f * (float)(t - 3); Sm[t] = S[t] + -5.0f; W[t] = 0u; }   // 0 = no predecessor (see fxg_clip_row_packed)
-    const int early_rows = (A - 4 < rows) ? (A - 4 > 0 ? A - 4 : 0) : rows;  // rows where "t - 3 > q" can still hold for some t < A
-    int q = 0;
-    if (rows > 0) {                                                           // row 0: every cell may start a path
-        const u32 c = rd[0];
-        first_n = (c == (u32)'N' && 0 < len) ? 0 : first_n;
-        if (early_rows > 0) fxg_clip_row_packed<AMAX, true, true, TN>(a, A, c, 0, 0u, S, Sm, W, best, bw, bq);
-        else fxg_clip_row_packed<AMAX, false, true, TN>(a, A, c, 0, 0u, S, Sm, W, best, bw, bq);
-        q = 1;
-    }
-    // The row's base comes out of LDS one row AHEAD of its use (rows >= 1 always exists in the staged tile: the bases of the next
-    // read or the tile's slack follow), so the load's latency is never waited for at the top of a row.
-    // wave-uniform loops (fxg_wave_max above): the early form tests the row number itself, so it serves every lane while ANY lane is early
-    const int early_u = UR ? early_rows : fxg_wave_max(early_rows), rows_u = UR ? rows : fxg_wave_max(rows);
-#pragma unroll 1
-    for (; q < early_u; ++q) {
-        if (q >= rows) continue;
-        const u32 c = rd[q];
-        first_n = (c == (u32)'N' && first_n == len && q < len) ? q : first_n;
-        fxg_clip_row_packed<AMAX, true, false, TN>(a, A, c, q, (u32)q, S, Sm, W, best, bw, bq);
-    }
-#pragma unroll 1
-    for (; q < rows_u; ++q) {
-        if (q >= rows) continue;
-        const u32 c = rd[q];
-        first_n = (c == (u32)'N' && first_n == len && q < len) ? q : first_n;
-        fxg_clip_row_packed<AMAX, false, false, TN>(a, A, c, q, (u32)q, S, Sm, W, best, bw, bq);
-    }
-}
 
 // ------------------------------------------------------------------------------------------------
 // Two passes for adapters up to 16 bases (every BASELINE config).  Only ONE cell's path summary is ever used -- the first maximum's --
@@ -311,49 +193,17 @@ FXG_HD void fxg_clip_rows_packed(const FxgKArgs &a, const uint8_t *rd, int len, 
 // Pass 1 therefore carries SCORES only (5 VALU instructions per cell instead of 15): it finds the row of the first maximum
 // (first row whose maximum exceeds everything before it) and keeps checkpoints of the score row every C = SPAN / 2 rows -- three
 // live ones, P[j % 3] = the row before chunk j.  When the best moves in chunk j, the checkpoint two chunks back (2 C >= SPAN - 1 rows
-// before the chunk's first row) is remembered.  Pass 2 restarts the summary-carrying DP (fxg_clip_row_packed) from that checkpoint
+// before the chunk's first row) is remembered.  Pass 2 restarts the summary-carrying DP (fxg_clip_row_packed_t) from that checkpoint
 // and runs at most 3 C rows up to the best row; the scores it recomputes are the same fp32 operations in the same order, the
 // summaries of cells whose paths started before the checkpoint are garbage, and the best cell's path is not one of them.
 // Row 0 needs no variant of its own here: the virtual cells above it carry the summary a path entering diagonally at (0, t) starts
-// from ((t << 19) + one step, what FIRST computes on the spot), and gap moves out of the border never win (above).
+// from ((t << 19) + one step), and gap moves out of the border never win (above).
 // ------------------------------------------------------------------------------------------------
 template <int AMAX> struct FxgClip2 {
     static constexpr int SPAN = AMAX + (AMAX + 1) / 5;
     static constexpr int C = SPAN / 2 > 0 ? SPAN / 2 : 1;      // ceil((SPAN - 1) / 2)
     static constexpr int WIN = 3 * C;
 };
-
-// one row of pass 1: scores only; returns the row's maximum over the adapter's columns.  One sweep (the cell above-left is saved
-// as the sweep passes it): with four waves per SIMD a wave issues every 6-10 cycles, which covers the dependent max3 -> add chain,
-// so nothing is gained by computing the diagonal candidates of the whole row first -- and that form copied the row every time.
-template <int AMAX, bool EARLY>
-FXG_HD float fxg_clip_row_score(const FxgKArgs &a, int A, u32 c, int q, float (&S)[AMAX], float (&Sm)[AMAX])
-{
-    const bool qn = (c == (u32)'N');
-    const float pair_eq = qn ? 0.1f : 1.0f, pair_ne = qn ? 0.1f : -1.0f;                 // sequence_alignment.h:157-169 (adapter without N)
-    float uSm = -5.0f, rowmax = -1000000.0f;                                             // S[q][-1] - 5
-    constexpr int AMIN = AMAX <= 4 ? 1 : (AMAX <= 8 ? 5 : AMAX);      // smallest adapter of the bucket: columns below it always count
-    // The match masks of the whole row first: a lane mask needs two wait states between the v_cmp that writes it and the v_cndmask
-    // that reads it, and with the compare right in front of its select the compiler paid them in s_nops (11 per row).
-    bool eq[AMAX];
-#pragma unroll
-    for (int t = 0; t < AMAX; ++t) eq[t] = (c == (u32)(uint8_t)a.adapter[t]);
-    // the diagonal candidate of column t + 1 is taken from S[t] BEFORE the sweep overwrites S[t]: every array is updated in place
-    float ul = 0.0f + (eq[0] ? pair_eq : pair_ne);                                       // S[q-1][-1] = query_border = 0
-#pragma unroll
-    for (int t = 0; t < AMAX; ++t) {
-        float ul_next = 0.0f;
-        if (t + 1 < AMAX) ul_next = S[t] + (eq[t + 1] ? pair_eq : pair_ne);
-        float left = Sm[t];
-        if (EARLY && t > 3) left = (t - 3 > q) ? -100000.0f : left;                      // sequence_alignment.cpp:387-389
-        const float sc = fmaxf(fmaxf(ul, uSm), left);
-        const float scm = sc + -5.0f;
-        S[t] = sc; Sm[t] = scm; uSm = scm; ul = ul_next;
-        if (t < AMIN) rowmax = fmaxf(rowmax, sc);
-        else rowmax = (t < A) ? fmaxf(rowmax, sc) : rowmax;
-    }
-    return rowmax;
-}
 
 // ------------------------------------------------------------------------------------------------
 // Pair values out of an LDS table (round 6).  A cell's pair score depends on (read base, adapter column) only, and a wave's lanes hold
@@ -375,11 +225,7 @@ FXG_HD float fxg_clip_row_score(const FxgKArgs &a, int A, u32 c, int q, float (&
 // ------------------------------------------------------------------------------------------------
 #define FXG_PTAB_LUT_BYTES 512u
 #define FXG_PTAB_ROW_BYTES 64u
-#ifdef FXG_NO_PTAB      // A/B builds (scripts/clip_ab.py): the compare + select cell of rounds 3-5
-__host__ __device__ constexpr bool fxg_clip_uses_ptab(int) { return false; }
-#else
 __host__ __device__ constexpr bool fxg_clip_uses_ptab(int amax) { return amax < 0; }                     // every packed instance: the register two-pass forms and the 17..99-column forms
-#endif
 // rows of the table for this adapter: "other", 'N', and one per distinct byte of the adapter
 FXG_HD u32 fxg_ptab_rows(const char *adapter, int alen)
 {
@@ -435,8 +281,8 @@ FXG_HD void fxg_clip_ptab_build(const FxgKArgs &a, uint8_t *ptab, u32 tid, u32 n
 }
 
 // A scheduling fence on either side of the fetch of the next row's values: left alone the scheduler sinks the fetch to the end of the row and the next
-// row begins by waiting for it (FXG_NO_PTAB_SCHED: A/B; pass 1 alone 2.33 -> 2.25 ms per 20 M reads of 100 bases, 1.89 without any fetch: profiles/r06/)
-#if !defined(FXG_NO_PTAB_SCHED) && !defined(FXG_HOST_EMULATION)
+// row begins by waiting for it (without the fences 2.33, with them 2.25 ms per 20 M reads of 100 bases for pass 1 alone, 1.89 without any fetch: profiles/r06/)
+#ifndef FXG_HOST_EMULATION
 #define FXG_SCHED_FENCE() __builtin_amdgcn_sched_barrier(0)
 #else
 #define FXG_SCHED_FENCE() ((void)0)
@@ -444,16 +290,7 @@ FXG_HD void fxg_clip_ptab_build(const FxgKArgs &a, uint8_t *ptab, u32 tid, u32 n
 
 // the gap penalty as a register operand: as a 32-bit literal it makes every `S - 5` an 8-byte instruction (v_add_f32 with a literal issues at 1.83
 // instead of 1.64 cycles at four waves per SIMD, scripts/ubench/valu_rate.hip 58)
-FXG_HD float fxg_minus5()
-{
-    float v = -5.0f;
-#if defined(FXG_M5_SGPR) && !defined(FXG_HOST_EMULATION)
-    asm volatile("" : "+s"(v));
-#elif defined(FXG_M5_VGPR) && !defined(FXG_HOST_EMULATION)
-    asm volatile("" : "+v"(v));
-#endif
-    return v;
-}
+FXG_HD float fxg_minus5() { return -5.0f; }
 
 // the table rows at offset `off` into registers: pair values, and (STEPS) what a diagonal step adds to the path summary
 template <int AMAX, bool STEPS>
@@ -469,8 +306,9 @@ FXG_HD void fxg_ptab_fetch(const uint8_t *ptab, u32 off, u32 step_off, u32 (&pr)
     }
 }
 
-// One row of scores with the pair values in pr (this row's table row).  pr (and st, STEPS) are replaced by the rows at offset `o_next` as soon as
-// the diagonal candidates are taken -- the up/left chain of the row covers the fetch.
+// One row of scores with the pair values in pr (this row's table row); returns the row's maximum over the adapter's columns.  S and Sm as in
+// fxg_clip_row_packed_t.  pr (and st, STEPS) are replaced by the rows at offset `o_next` as soon as the diagonal candidates are taken -- the up/left
+// chain of the row covers the fetch.
 template <int AMAX, bool EARLY, bool STEPS = false>
 FXG_HD float fxg_clip_row_score_t(int A, int q, float (&S)[AMAX], float (&Sm)[AMAX], u32 (&pr)[16], u32 (&st)[16], const uint8_t *ptab, u32 o_next, u32 step_off)
 {
@@ -480,9 +318,7 @@ FXG_HD float fxg_clip_row_score_t(int A, int q, float (&S)[AMAX], float (&Sm)[AM
 #pragma unroll
     for (int t = 0; t < AMAX; ++t) ul[t] = (t ? S[t - 1] : 0.0f) + __builtin_bit_cast(float, pr[t]);
     FXG_SCHED_FENCE();
-#ifndef FXG_ABL_NOFETCH      // (timing experiment: the row without its fetch -- wrong results)
     fxg_ptab_fetch<AMAX, STEPS>(ptab, o_next, step_off, pr, st);      // the next row's values, into the registers this row no longer needs
-#endif
     FXG_SCHED_FENCE();
     const float m5 = fxg_minus5();
     float uSm = -5.0f, rowmax = -1000000.0f;                                             // S[q][-1] - 5
@@ -499,8 +335,20 @@ FXG_HD float fxg_clip_row_score_t(int A, int q, float (&S)[AMAX], float (&Sm)[AM
     return rowmax;
 }
 
-// One row of pass 2 (fxg_clip_row_packed<.., FIRST = false, TN = false>: the same cell, the same summary word) with the pair values and the
-// diagonal's summary steps out of the table: ul = S[q-1][t-1] + pr[t], wd = W[q-1][t-1] + st[t].
+// One row of pass 2 of fxg_clip_two_pass, with the pair values and the diagonal's summary steps out of the table: ul = S[q-1][t-1] + pr[t],
+// wd = W[q-1][t-1] + st[t].
+// W holds every cell's summary ALREADY extended by one gap step (w + SZ1): that is what both the cell below (up) and the cell to
+// the right in the next row (left) need, so the step is added once per cell instead of once per use; the diagonal adds the
+// difference.  "No predecessor" is the value 0, which no extended summary can be (its path_len is >= 2).
+// Sm holds every cell's score minus the gap penalty for the same reason (one subtraction serves `up` and `left`).
+// Cell rule (sequence_alignment.cpp:380-417): strict '>' from diag to up to left, i.e. the maximum with ties going to diag, then up:
+//   score = max3(ul, up, left); diag iff score == ul; else up iff score == up; else left.
+// The "path enters the matrix here" test can only fire where a predecessor lies outside the matrix: anywhere in row 0, and in column 0
+// of the other rows.  The virtual cells above row 0 carry the summary a path entering there starts from (fxg_clip_two_pass), so the row
+// tests it at t == 0 only.
+// TRACK = false: the row cannot hold the first maximum (the second pass knows its row) -- no best-cell update.
+// vstart: what a path that enters the matrix in this row records as its query_start (8 bits): the row relative to the first summary row
+// of the second pass -- which is what lets that form take reads of any length.
 template <int AMAX, bool EARLY, bool TRACK>
 FXG_HD void fxg_clip_row_packed_t(int A, int q, u32 vstart, float (&S)[AMAX], float (&Sm)[AMAX], u32 (&W)[AMAX], float &best, u32 &bw, u32 &bq,
                                   u32 (&pr)[16], u32 (&st)[16], const uint8_t *ptab, u32 o_next, u32 step_off)
@@ -539,6 +387,9 @@ FXG_HD void fxg_clip_row_packed_t(int A, int q, u32 vstart, float (&S)[AMAX], fl
         const float scm = sc + m5;
         S[t] = sc; Sm[t] = scm; W[t] = wp;
         uSm = scm; uW = wp;
+        // first maximum in query-major order.  Columns past the adapter (t >= A) do not count; the smallest adapter of this
+        // bucket has AMIN bases, so only columns t >= AMIN need the test (none for the exact buckets 9..16) -- a mask that went
+        // through a scalar AND costs a v_cndmask several times what a mask straight from a v_cmp does (scripts/ubench/valu_rate.hip).
         constexpr int AMIN = AMAX <= 4 ? 1 : (AMAX <= 8 ? 5 : (AMAX <= 16 ? AMAX : AMAX - 3));
         if (!TRACK) continue;
         if (t < AMIN) {
@@ -604,7 +455,7 @@ FXG_HD int fxg_clip_first_n(const uint8_t *rd, int len, int len_u, u32 stride, i
 // GL: `rd` points into the batch in global memory instead of a staged copy in LDS (fxg_plan.h: clip_global).  Pass 1, whose row number is a
 // scalar, then takes the row's base out of a two-dword window that moves on every fourth row (one 4-byte load per lane and four rows: byte loads,
 // each lane on a line of its own, would cost the CU's vector cache a lookup per lane and row); pass 2 and the N scan touch ~20 rows and read them directly.
-// ptab (staged form): the workgroup's pair table (fxg_clip_ptab_build) -- pass 1 then takes its pair values from it (fxg_clip_row_score_t)
+// ptab: the workgroup's pair table (fxg_clip_ptab_build), out of which both passes take their pair values and pass 2 its summary steps
 template <int AMAX, bool GL = false>
 FXG_HD int fxg_clip_two_pass(const FxgKArgs &a, const uint8_t *rd, int len, int rows, float &best, u32 &bw, u32 &bq, int &first_n, const bool UR = false, const uint8_t *ptab = nullptr)
 {
@@ -619,36 +470,24 @@ FXG_HD int fxg_clip_two_pass(const FxgKArgs &a, const uint8_t *rd, int len, int 
     const int rows_u = UR ? rows : fxg_wave_max(rows > 0 ? rows : 0);
     if (rows_u <= 0) return 0;
     // ---- pass 1 ----
-#if defined(FXG_ABL_ROWCLK) && !defined(FXG_HOST_EMULATION)      // timing experiment: shader cycles a wave spends in the row loops of either pass, and the rows it ran
-    const u64 clk_a = __builtin_amdgcn_s_memtime();
-#endif
     float b1 = -1000000.0f;
     int q = 0, r0 = 0, bq1 = 0;
     u32 cn = 0u, gw0 = 0u, gw1 = 0u;
     int gmax = 0;                                           // GL: last dword of the array that may be read, counted from this row's first
-    // staged form: pr / mult = the pair values of row q, on = table offset of row q + 1, cn = the base of row q + 2 -- each fetched a row or more ahead of its use
-    constexpr bool PT = fxg_clip_uses_ptab(-AMAX);
+    // pr = the pair values of row q, on = table offset of row q + 1, cn = the base of row q + 2 (staged form) -- each fetched a row or more ahead of its use
     u32 pr[16] = {}, st[16] = {}, on = 0u;
-    const u32 step_off = PT ? a.clip_ptab_rows * a.clip_ptab_stride : 0u;      // from a byte's pair row to its step row
+    const u32 step_off = a.clip_ptab_rows * a.clip_ptab_stride;      // from a byte's pair row to its step row
+    const uint16_t *lut = reinterpret_cast<const uint16_t *>(ptab);
     if constexpr (GL) {
         gmax = fxg_gl_last_dword(a.clip_total, (u64)(rd - a.clip_src));
         gw0 = fxg_ld32(rd, 0, gmax); gw1 = fxg_ld32(rd, 1, gmax);
-        if constexpr (PT) {
-            const uint16_t *lut = reinterpret_cast<const uint16_t *>(ptab);
-            on = lut[(gw0 >> 8) & 0xFFu];
-            fxg_ptab_fetch<AMAX, false>(ptab, lut[gw0 & 0xFFu], step_off, pr, st);
-        }
-    } else if constexpr (PT) {
-        const uint16_t *lut = reinterpret_cast<const uint16_t *>(ptab);
+        on = lut[(gw0 >> 8) & 0xFFu];
+        fxg_ptab_fetch<AMAX, false>(ptab, lut[gw0 & 0xFFu], step_off, pr, st);
+    } else {
         const u32 o0 = lut[rd[0]];
         on = lut[rd[1]]; cn = rd[2];
         fxg_ptab_fetch<AMAX, false>(ptab, o0, step_off, pr, st);
-    } else cn = rd[0];
-#ifdef FXG_ABL_NOLUT         // (timing experiment: no base / lut reads in the row loop -- wrong results)
-#define FXG_ABL_LUT_READS const u32 on2 = on;
-#else
-#define FXG_ABL_LUT_READS const u32 on2 = reinterpret_cast<const uint16_t *>(ptab)[cn]; cn = rd[q + 3];
-#endif
+    }
     // chunk j = rows [j C, j C + C): saves the row before it in Psave = P[j % 3]; the restart row for a best found in it is
     // Pwin = P[(j + 1) % 3] = the row before chunk j - 2 (before chunk 0 for j < 2: the border, which all three start from)
 #define FXG_CLIP_CHUNK(EARLY, Psave, Pwin)                                                                                   \
@@ -658,26 +497,17 @@ FXG_HD int fxg_clip_two_pass(const FxgKArgs &a, const uint8_t *rd, int len, int 
         bool upd = false;                                                                                                    \
         _Pragma("unroll 1") for (; q < qend; ++q) {                                                                          \
             float rm;                                                                                                        \
-            if constexpr (GL && PT) {            /* the base of row q + 2 out of the window (q is a scalar), its table offset a row ahead of the fetch */ \
+            if constexpr (GL) {                  /* the base of row q + 2 out of the window (q is a scalar), its table offset a row ahead of the fetch */ \
                 const u32 ca = ((((q + 2) >> 2) == (q >> 2) ? gw0 : gw1) >> ((u32)((q + 2) & 3) << 3)) & 0xFFu;             \
-                const u32 on2 = reinterpret_cast<const uint16_t *>(ptab)[ca];                                                \
+                const u32 on2 = lut[ca];                                                                                     \
                 if ((q & 3) == 3) { gw0 = gw1; gw1 = fxg_ld32(rd, (q >> 2) + 2, gmax); }                                     \
                 if (!UR && q >= rows) continue;                                                                              \
                 rm = fxg_clip_row_score_t<AMAX, EARLY>(A, q, S, Sm, pr, st, ptab, on, step_off);                             \
                 on = on2;                                                                                                    \
-            } else if constexpr (GL) {                                                                                       \
-                const u32 c = (gw0 >> ((u32)(q & 3) << 3)) & 0xFFu;                                                          \
-                if ((q & 3) == 3) { gw0 = gw1; gw1 = fxg_ld32(rd, (q >> 2) + 2, gmax); }                                     \
-                if (!UR && q >= rows) continue;                                                                              \
-                rm = fxg_clip_row_score<AMAX, EARLY>(a, A, c, q, S, Sm);                                                     \
-            } else if constexpr (!PT) {                                                                                      \
-                const u32 c = cn;                                                                                            \
-                cn = rd[q + 1];                                                                                              \
-                if (!UR && q >= rows) continue;                                                                              \
-                rm = fxg_clip_row_score<AMAX, EARLY>(a, A, c, q, S, Sm);                                                     \
             } else {                                                                                                         \
                 if (!UR && q >= rows) continue;          /* (a lane past its rows never comes back: its fetch state may lapse) */ \
-                FXG_ABL_LUT_READS                                                                                            \
+                const u32 on2 = lut[cn];                                                                                     \
+                cn = rd[q + 3];                                                                                              \
                 rm = fxg_clip_row_score_t<AMAX, EARLY>(A, q, S, Sm, pr, st, ptab, on, step_off);                             \
                 on = on2;                                                                                                    \
             }                                                                                                                \
@@ -701,10 +531,6 @@ FXG_HD int fxg_clip_two_pass(const FxgKArgs &a, const uint8_t *rd, int len, int 
         FXG_CLIP_CHUNK(false, P1, P2)
     }
 #undef FXG_CLIP_CHUNK
-#if defined(FXG_ABL_ROWCLK) && !defined(FXG_HOST_EMULATION)
-    const u64 clk_b = __builtin_amdgcn_s_memtime();
-    if ((threadIdx.x & 63u) == 0u) { atomicAdd(reinterpret_cast<u64 *>(a.errflag + 10) + 0, clk_b - clk_a); atomicAdd(reinterpret_cast<u64 *>(a.errflag + 10) + 1, (u64)rows_u); }
-#endif
     if (rows <= 0) return 0;                                // (only now: the loops above are the wave's, not the lane's)
     if (FXG_DBG(a, 32u)) { best = b1; bq = (u32)bq1; bw = 0u; return 0; }      // ablation builds: pass 1 alone (wrong results, timing only)
     // ---- pass 2: rows r0 .. bq1 with the path summaries, from the checkpoint; only row bq1 can hold the first maximum ----
@@ -712,83 +538,56 @@ FXG_HD int fxg_clip_two_pass(const FxgKArgs &a, const uint8_t *rd, int len, int 
 #pragma unroll
     for (int t = 0; t < AMAX; ++t) { S[t] = CB[t]; Sm[t] = CB[t] + -5.0f; W[t] = ((u32)(t + 1) << 19) + FXG_PK_SZ1; }
     q = r0;
-    if constexpr (PT) {
-        // The best path covers at most SPAN rows (above), i.e. starts in row rs = bq1 - SPAN + 1 or later: rows r0 .. rs - 1 re-run the SCORES only
-        // (the cheap row of pass 1), rows rs .. bq1 carry the summaries, whose start field counts from rs.  Every lane is at rows of its own
-        // here; the fetch pipeline is the one of pass 1 (values of row q in registers, table offset of row q + 1, base of row q + 2).
-        // GL: the look-ahead bases of rows past bq1 are fetched but never scored; they are read at the row's last byte instead (rows - 1 >= bq1):
-        // row bq1 may be the array's last byte (the batch's last read at len == stride), and q + 3 would run up to two bytes past it.  (The
-        // staged form reads its tile in LDS, where a look-ahead past the tile cannot fault; it keeps the unclamped index.)
-        constexpr int SPAN = FxgClip2<AMAX>::SPAN;
-        const int rs = bq1 - SPAN + 1 > r0 ? bq1 - SPAN + 1 : r0;
-        const uint16_t *lut = reinterpret_cast<const uint16_t *>(ptab);
-        const int qlast = rows - 1;
+    // The best path covers at most SPAN rows (above), i.e. starts in row rs = bq1 - SPAN + 1 or later: rows r0 .. rs - 1 re-run the SCORES only
+    // (the cheap row of pass 1), rows rs .. bq1 carry the summaries, whose start field counts from rs.  Every lane is at rows of its own
+    // here; the fetch pipeline is the one of pass 1 (values of row q in registers, table offset of row q + 1, base of row q + 2).
+    // GL: the look-ahead bases of rows past bq1 are fetched but never scored; they are read at the row's last byte instead (rows - 1 >= bq1):
+    // row bq1 may be the array's last byte (the batch's last read at len == stride), and q + 3 would run up to two bytes past it.  (The
+    // staged form reads its tile in LDS, where a look-ahead past the tile cannot fault; it keeps the unclamped index.)
+    constexpr int SPAN = FxgClip2<AMAX>::SPAN;
+    const int rs = bq1 - SPAN + 1 > r0 ? bq1 - SPAN + 1 : r0;
+    const int qlast = rows - 1;
 #define FXG_RD_AHEAD(i) rd[GL && (i) > qlast ? qlast : (i)]
-        {
-            const u32 o0 = lut[rd[q]];
-            on = lut[FXG_RD_AHEAD(q + 1)]; cn = FXG_RD_AHEAD(q + 2);
-            fxg_ptab_fetch<AMAX, true>(ptab, o0, step_off, pr, st);
-        }
-        const int n0 = rs - r0, n0u = fxg_wave_max(n0);
-#pragma unroll 1
-        for (int i = 0; i < n0u; ++i) {
-            if (i >= n0) continue;
-            const u32 on2 = lut[cn];
-            cn = FXG_RD_AHEAD(q + 3);
-            (void)fxg_clip_row_score_t<AMAX, true, true>(A, q, S, Sm, pr, st, ptab, on, step_off);      // (the early form tests the row number itself)
-            on = on2; ++q;
-        }
-        // summary row i is read row rs + i >= i: rows past i = A - 4 are past the early rule, so the first A - 4 run in the early form (which tests the
-        // row number itself) in EVERY lane and the two loops have the same trip counts across the wave -- a split by the lane's own rows would
-        // make the wave issue both forms for as many rows as its slowest lane needs of each
-        const int win = bq1 - rs, n1 = win < early_rows ? win : early_rows, n2 = win - n1;
-        const int n1u = fxg_wave_max(n1), n2u = fxg_wave_max(n2);
-#pragma unroll 1
-        for (int i = 0; i < n1u; ++i) {
-            if (i >= n1) continue;
-            const u32 on2 = lut[cn];
-            cn = FXG_RD_AHEAD(q + 3);
-            fxg_clip_row_packed_t<AMAX, true, false>(A, q, (u32)(q - rs), S, Sm, W, best, bw, bq, pr, st, ptab, on, step_off);
-            on = on2; ++q;
-        }
-#pragma unroll 1
-        for (int i = 0; i < n2u; ++i) {
-            if (i >= n2) continue;
-            const u32 on2 = lut[cn];
-            cn = FXG_RD_AHEAD(q + 3);
-            fxg_clip_row_packed_t<AMAX, false, false>(A, q, (u32)(q - rs), S, Sm, W, best, bw, bq, pr, st, ptab, on, step_off);
-            on = on2; ++q;
-        }
-        fxg_clip_row_packed_t<AMAX, true, true>(A, bq1, (u32)(bq1 - rs), S, Sm, W, best, bw, bq, pr, st, ptab, on, step_off);
-#undef FXG_RD_AHEAD
-#if defined(FXG_ABL_ROWCLK) && !defined(FXG_HOST_EMULATION)
-        if ((threadIdx.x & 63u) == 0u) { atomicAdd(reinterpret_cast<u64 *>(a.errflag + 10) + 2, __builtin_amdgcn_s_memtime() - clk_b); atomicAdd(reinterpret_cast<u64 *>(a.errflag + 10) + 3, (u64)(n0u + n1u + n2u + 1)); atomicAdd(reinterpret_cast<u64 *>(a.errflag + 10) + 4, (u64)n0u); }
-#endif
-        if (!(a.clip_flags & FXG_CLIP_KEEP_N)) first_n = fxg_clip_first_n(rd, len, UR ? len : fxg_wave_max(len), a.clip_stride, first_n);
-        return rs;
+    {
+        const u32 o0 = lut[rd[q]];
+        on = lut[FXG_RD_AHEAD(q + 1)]; cn = FXG_RD_AHEAD(q + 2);
+        fxg_ptab_fetch<AMAX, true>(ptab, o0, step_off, pr, st);
     }
-    // window row i is read row r0 + i >= i: rows past i = A - 4 are past the early rule.  n1 rows in the early form, n2 in the other;
-    // both loops run the wave's maximum, a lane beyond its own count skips the row
-    const int win = bq1 - r0, n1 = win < early_rows ? win : early_rows, n2 = win - n1;
+    const int n0 = rs - r0, n0u = fxg_wave_max(n0);
+#pragma unroll 1
+    for (int i = 0; i < n0u; ++i) {
+        if (i >= n0) continue;
+        const u32 on2 = lut[cn];
+        cn = FXG_RD_AHEAD(q + 3);
+        (void)fxg_clip_row_score_t<AMAX, true, true>(A, q, S, Sm, pr, st, ptab, on, step_off);      // (the early form tests the row number itself)
+        on = on2; ++q;
+    }
+    // summary row i is read row rs + i >= i: rows past i = A - 4 are past the early rule, so the first A - 4 run in the early form (which tests the
+    // row number itself) in EVERY lane and the two loops have the same trip counts across the wave -- a split by the lane's own rows would
+    // make the wave issue both forms for as many rows as its slowest lane needs of each
+    const int win = bq1 - rs, n1 = win < early_rows ? win : early_rows, n2 = win - n1;
     const int n1u = fxg_wave_max(n1), n2u = fxg_wave_max(n2);
 #pragma unroll 1
     for (int i = 0; i < n1u; ++i) {
         if (i >= n1) continue;
-        fxg_clip_row_packed<AMAX, true, false, false, false>(a, A, (u32)rd[q], q, (u32)(q - r0), S, Sm, W, best, bw, bq);
-        ++q;
+        const u32 on2 = lut[cn];
+        cn = FXG_RD_AHEAD(q + 3);
+        fxg_clip_row_packed_t<AMAX, true, false>(A, q, (u32)(q - rs), S, Sm, W, best, bw, bq, pr, st, ptab, on, step_off);
+        on = on2; ++q;
     }
 #pragma unroll 1
     for (int i = 0; i < n2u; ++i) {
         if (i >= n2) continue;
-        fxg_clip_row_packed<AMAX, false, false, false, false>(a, A, (u32)rd[q], q, (u32)(q - r0), S, Sm, W, best, bw, bq);
-        ++q;
+        const u32 on2 = lut[cn];
+        cn = FXG_RD_AHEAD(q + 3);
+        fxg_clip_row_packed_t<AMAX, false, false>(A, q, (u32)(q - rs), S, Sm, W, best, bw, bq, pr, st, ptab, on, step_off);
+        on = on2; ++q;
     }
-    fxg_clip_row_packed<AMAX, true, false, false, true>(a, A, (u32)rd[bq1], bq1, (u32)(bq1 - r0), S, Sm, W, best, bw, bq);
+    fxg_clip_row_packed_t<AMAX, true, true>(A, bq1, (u32)(bq1 - rs), S, Sm, W, best, bw, bq, pr, st, ptab, on, step_off);
+#undef FXG_RD_AHEAD
     // the -n rule needs the first N of the read itself (fastx_clipper.cpp:306-311); nothing else does
-    if (!(a.clip_flags & FXG_CLIP_KEEP_N)) {
-        first_n = fxg_clip_first_n(rd, len, UR ? len : fxg_wave_max(len), a.clip_stride, first_n);
-    }
-    return r0;
+    if (!(a.clip_flags & FXG_CLIP_KEEP_N)) first_n = fxg_clip_first_n(rd, len, UR ? len : fxg_wave_max(len), a.clip_stride, first_n);
+    return rs;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -802,27 +601,18 @@ FXG_HD int fxg_clip_two_pass(const FxgKArgs &a, const uint8_t *rd, int len, int 
 // bases, 1 040 at 32 and 200 from 33 on -- profiles/r03/u_clip_by_adapter_len_before.txt).
 // The virtual cells above row 0 carry the summary a path entering diagonally at (0, t) starts from, as in fxg_clip_two_pass.
 // ------------------------------------------------------------------------------------------------
-#if defined(FXG_HOST_EMULATION) || defined(FXG_NO_KEEP_V)
-#define FXG_KEEP_V(x) ((void)0)
-#else
-#define FXG_KEEP_V(x) asm volatile("" : "+v"(x))
-#endif
 #define FXG_K_MAT1 1u
 #define FXG_K_DIA1 (1u << 7)
 #define FXG_K_SZ1  (1u << 14)
 #define FXG_K_START(v) ((u32)(v) << 23)
 // smallest adapter of the bucket AMAX (fxg_plan.h): columns below it always count towards the best cell
-__host__ __device__ constexpr int fxg_clip_k_amin(int amax, bool tn = false)
+__host__ __device__ constexpr int fxg_clip_k_amin(int amax)
 {
-    return tn ? (amax <= 16 ? 1 : amax <= 24 ? 17 : amax <= 36 ? 25 : amax <= 48 ? 37 : amax <= 64 ? 49 : 65)        // buckets 16 24 36 48 64 100 (builds without the pair table: adapters with N)
-              : (amax <= 16 ? 1 : amax <= 20 ? 17 : amax <= 64 ? amax - 3 : amax <= 88 ? amax - 7 : 89);             // buckets every 4 columns to 64, every 8 to 88, then 100 (fxg_plan.h)
+    return amax <= 16 ? 1 : amax <= 20 ? 17 : amax <= 64 ? amax - 3 : amax <= 88 ? amax - 7 : 89;      // buckets every 4 columns to 64, every 8 to 88, then 100 (fxg_plan.h)
 }
 template <int AMAX> struct FxgClipK { static constexpr bool SM = AMAX <= 24; static constexpr int NSM = SM ? AMAX : 1; };
 
-// TN: the adapter may contain 'N' (sequence_alignment.h:157-169: a neutral pair scores 0.1, N against N 0.0, and counts neither as match
-// nor as mismatch).  Which columns are N is the same for every lane, so it costs scalar selects of the masks and two more VALU
-// instructions per cell (the pair value and the diagonal's step each take one more select); the instances without it are unchanged.
-// The rows of the 17..99-column forms with the pair table (round 6): block b of a table row holds the pair values of columns 4 b .. 4 b + 3, the step row
+// The rows of the 17..99-column forms take their pair values out of the pair table (round 6): block b of a table row holds the pair values of columns 4 b .. 4 b + 3, the step row
 // what a diagonal step into them adds to the summary.  The sweep is in place -- the diagonal candidate of column t + 1 is taken from column t before the sweep
 // overwrites it -- so it needs value t + 1 while it is at column t: the current block and the next one are kept (one ds_read_b128 each for pairs and steps per
 // four columns, requested a block ahead of their first use: 16 registers), and the cell is add, add, max3, two compares, two selects, add, add -- no compare
@@ -832,7 +622,7 @@ FXG_HD void fxg_clip_row_kt(const FxgKArgs &a, int A, u32 c, int q, u32 vstart, 
                             float &best, u32 &bw, u32 &bq, const uint8_t *ptab)
 {
     constexpr bool SM = FxgClipK<AMAX>::SM;
-    constexpr int AMIN = fxg_clip_k_amin(AMAX, false);
+    constexpr int AMIN = fxg_clip_k_amin(AMAX);
     const u32 po = reinterpret_cast<const uint16_t *>(ptab)[c & 0xFFu];
     const u32x4 *pp = reinterpret_cast<const u32x4 *>(ptab + po), *sp = reinterpret_cast<const u32x4 *>(ptab + po + a.clip_ptab_rows * a.clip_ptab_stride);
     const float best_in = best, m5 = fxg_minus5();
@@ -869,7 +659,7 @@ FXG_HD void fxg_clip_row_kt(const FxgKArgs &a, int A, u32 c, int q, u32 vstart, 
                 w = isu ? uW : W[t];
                 w = isd ? wd : w;
             }
-            const u32 wp = w + FXG_K_SZ1;                                                // stored already extended by one gap step, see fxg_clip_row_packed
+            const u32 wp = w + FXG_K_SZ1;                                                // stored already extended by one gap step, see fxg_clip_row_packed_t
             const float scm = sc + m5;
             S[t] = sc; W[t] = wp;
             if (SM) Sm[SM ? t : 0] = scm;
@@ -889,12 +679,21 @@ FXG_HD void fxg_clip_row_kt(const FxgKArgs &a, int A, u32 c, int q, u32 vstart, 
     if (TRACK) bq = (best > best_in) ? (u32)q : bq;
 }
 
+// What the drivers call.  The row stays one inlining level below it: called directly, the four-wave instances (20..36 columns) come out
+// differently (10 kernels, 200 instructions more in all) -- a code change that would need a GPU A/B of its own.
+template <int AMAX, bool EARLY, bool TRACK>
+FXG_HD void fxg_clip_row_k(const FxgKArgs &a, int A, u32 c, int q, u32 vstart, float (&S)[AMAX], float (&Sm)[FxgClipK<AMAX>::NSM], u32 (&W)[AMAX],
+                           float &best, u32 &bw, u32 &bq, const uint8_t *ptab)
+{
+    fxg_clip_row_kt<AMAX, EARLY, TRACK>(a, A, c, q, vstart, S, Sm, W, best, bw, bq, ptab);
+}
+
 // scores only (pass 1 of fxg_clip_two_pass_k and its re-run up to the first summary row)
 template <int AMAX, bool EARLY>
-FXG_HD float fxg_clip_row_score_kt(const FxgKArgs &a, int A, u32 c, int q, float (&S)[AMAX], float (&Sm)[AMAX], const uint8_t *ptab)
+FXG_HD float fxg_clip_row_score_k(const FxgKArgs &a, int A, u32 c, int q, float (&S)[AMAX], float (&Sm)[AMAX], const uint8_t *ptab)
 {
-    constexpr bool SM = AMAX <= 48;
-    constexpr int AMIN = fxg_clip_k_amin(AMAX, false);
+    constexpr bool SM = AMAX <= 48;                 // the score rows keep S - 5 as well where that still leaves room: nothing else is live while they run
+    constexpr int AMIN = fxg_clip_k_amin(AMAX);
     const u32 po = reinterpret_cast<const uint16_t *>(ptab)[c & 0xFFu];
     const u32x4 *pp = reinterpret_cast<const u32x4 *>(ptab + po);
     const float m5 = fxg_minus5();
@@ -926,76 +725,7 @@ FXG_HD float fxg_clip_row_score_kt(const FxgKArgs &a, int A, u32 c, int q, float
     return rowmax;
 }
 
-template <int AMAX, bool EARLY, bool TRACK, bool TN = false>
-FXG_HD void fxg_clip_row_k(const FxgKArgs &a, int A, u32 c, int q, u32 vstart, float (&S)[AMAX], float (&Sm)[FxgClipK<AMAX>::NSM], u32 (&W)[AMAX],
-                           float &best, u32 &bw, u32 &bq, const uint8_t *ptab = nullptr)
-{
-    if constexpr (fxg_clip_uses_ptab(-AMAX)) { fxg_clip_row_kt<AMAX, EARLY, TRACK>(a, A, c, q, vstart, S, Sm, W, best, bw, bq, ptab); return; }
-    constexpr bool SM = FxgClipK<AMAX>::SM;
-    constexpr int AMIN = fxg_clip_k_amin(AMAX, TN);
-    const bool qn = (c == (u32)'N');
-    const float pair_eq = qn ? 0.1f : 1.0f, pair_ne = qn ? 0.1f : -1.0f;                 // sequence_alignment.h:157-169 for an adapter base that is not N
-    const float pair_tn = qn ? 0.0f : 0.1f;                                              // ... and for one that is
-    const u32 dxr = qn ? 0u : FXG_K_DIA1;
-    const float best_in = best;
-    float uSm = -5.0f;                                                                   // S[q][-1] - 5
-    u32 uW = 0u;
-    const bool eq0 = (c == (u32)(uint8_t)a.adapter[0]);
-    const bool tn0 = TN && ((u32)(uint8_t)a.adapter[0] == (u32)'N');
-    float ul = 0.0f + (tn0 ? pair_tn : (eq0 ? pair_eq : pair_ne));                       // S[q-1][-1] = query_border = 0
-    u32 wd = tn0 ? 0u : dxr + (u32)eq0;                                                  // no predecessor left of column 0: the step alone
-#pragma unroll
-    for (int b0 = 0; b0 < AMAX; b0 += 16) {
-        // the match masks of the next 16 diagonals first (a lane mask needs two wait states between its v_cmp and the v_cndmask that reads it)
-        bool eq[16];
-#pragma unroll
-        for (int k = 0; k < 16; ++k) eq[k] = (b0 + k + 1 < AMAX) ? (c == (u32)(uint8_t)a.adapter[b0 + k + 1]) : false;
-#pragma unroll
-        for (int k = 0; k < 16; ++k) {
-            const int t = b0 + k;
-            if (t >= AMAX) break;
-            float ul_next = 0.0f;
-            u32 wd_next = 0u;
-            if (t + 1 < AMAX) {
-                const bool tn1 = TN && ((u32)(uint8_t)a.adapter[t + 1] == (u32)'N');      // uniform: a scalar condition
-                const float pv = eq[k] ? pair_eq : pair_ne;
-                ul_next = S[t] + (tn1 ? pair_tn : pv);
-                u32 wdx = W[t] + (tn1 ? 0u : dxr);
-                FXG_KEEP_V(wdx);                                                         // keeps "+ match" the carry-in of one v_addc_co_u32 (else: select 0/1, or, add)
-                wd_next = wdx + (u32)(eq[k] && !tn1);
-            }
-            float left = SM ? Sm[SM ? t : 0] : S[t] + -5.0f;
-            if (EARLY && t > 3) left = (t - 3 > q) ? -100000.0f : left;                  // sequence_alignment.cpp:387-389, rows q < A - 4 only
-            const float sc = fmaxf(fmaxf(ul, uSm), left);
-            const bool isd = (sc == ul), isu = (sc == uSm);                              // diag > up > left on ties (:380-417)
-            u32 w;
-            if (t == 0) {                                                                // diag and up come from outside the matrix: the path starts here
-                const u32 fresh = FXG_K_START(vstart) + FXG_K_SZ1 + (isd ? wd : 0u);
-                w = (isd || isu) ? fresh : W[0];
-            } else {
-                w = isu ? uW : W[t];
-                w = isd ? wd : w;
-            }
-            const u32 wp = w + FXG_K_SZ1;                                                // stored already extended by one gap step, see fxg_clip_row_packed
-            const float scm = sc + -5.0f;
-            S[t] = sc; W[t] = wp;
-            if (SM) Sm[SM ? t : 0] = scm;
-            uSm = scm; uW = wp; ul = ul_next; wd = wd_next;
-            if (!TRACK) continue;
-            if (t < AMIN) {
-                const bool gb = sc > best;
-                bw = gb ? w : bw;
-                best = fmaxf(best, sc);
-            } else {
-                const bool gb = (sc > best) && (t < A);
-                best = gb ? sc : best; bw = gb ? w : bw;
-            }
-        }
-    }
-    if (TRACK) bq = (best > best_in) ? (u32)q : bq;
-}
-
-template <int AMAX, bool TN>
+template <int AMAX>
 FXG_HD void fxg_clip_rows_k(const FxgKArgs &a, const uint8_t *rd, int len, int rows, float &best, u32 &bw, u32 &bq, int &first_n, const bool UR = false, const uint8_t *ptab = nullptr)
 {
     float S[AMAX], Sm[FxgClipK<AMAX>::NSM];
@@ -1019,7 +749,7 @@ FXG_HD void fxg_clip_rows_k(const FxgKArgs &a, const uint8_t *rd, int len, int r
         cn = rd[q + 1];
         if (!UR && q >= rows) continue;
         first_n = (c == (u32)'N' && first_n == len && q < len) ? q : first_n;
-        fxg_clip_row_k<AMAX, true, true, TN>(a, A, c, q, (u32)q, S, Sm, W, best, bw, bq, ptab);
+        fxg_clip_row_k<AMAX, true, true>(a, A, c, q, (u32)q, S, Sm, W, best, bw, bq, ptab);
     }
 #pragma unroll 1
     for (; q < rows_u; ++q) {
@@ -1027,7 +757,7 @@ FXG_HD void fxg_clip_rows_k(const FxgKArgs &a, const uint8_t *rd, int len, int r
         cn = rd[q + 1];
         if (!UR && q >= rows) continue;
         first_n = (c == (u32)'N' && first_n == len && q < len) ? q : first_n;
-        fxg_clip_row_k<AMAX, false, true, TN>(a, A, c, q, (u32)q, S, Sm, W, best, bw, bq, ptab);
+        fxg_clip_row_k<AMAX, false, true>(a, A, c, q, (u32)q, S, Sm, W, best, bw, bq, ptab);
     }
 }
 
@@ -1040,63 +770,11 @@ FXG_HD void fxg_clip_rows_k(const FxgKArgs &a, const uint8_t *rd, int len, int r
 // summaries (fxg_clip_row_k), and only row bq1 looks for the best cell.  A path that starts in pass 2 starts in column 0 (or in row 0
 // when r0 = 0), so its `start` is the row RELATIVE to r0: reads of any length fit the 9 bits.
 // ------------------------------------------------------------------------------------------------
-template <int AMAX, bool EARLY, bool TN>
-FXG_HD float fxg_clip_row_score_k(const FxgKArgs &a, int A, u32 c, int q, float (&S)[AMAX], float (&Sm)[AMAX], const uint8_t *ptab = nullptr)
-{
-    if constexpr (fxg_clip_uses_ptab(-AMAX)) return fxg_clip_row_score_kt<AMAX, EARLY>(a, A, c, q, S, Sm, ptab);
-    constexpr bool SM = AMAX <= 48;                 // the score rows keep S - 5 as well where that still leaves room: nothing else is live while they run
-    constexpr int AMIN = fxg_clip_k_amin(AMAX, TN);
-    const bool qn = (c == (u32)'N');
-    const float pair_eq = qn ? 0.1f : 1.0f, pair_ne = qn ? 0.1f : -1.0f;
-    const float pair_tn = qn ? 0.0f : 0.1f;
-    float uSm = -5.0f, rowmax = -1000000.0f;
-    const bool tn0 = TN && ((u32)(uint8_t)a.adapter[0] == (u32)'N');
-    float ul = 0.0f + (tn0 ? pair_tn : ((c == (u32)(uint8_t)a.adapter[0]) ? pair_eq : pair_ne));
-#pragma unroll
-    for (int b0 = 0; b0 < AMAX; b0 += 16) {
-        bool eq[16];
-#pragma unroll
-        for (int k = 0; k < 16; ++k) eq[k] = (b0 + k + 1 < AMAX) ? (c == (u32)(uint8_t)a.adapter[b0 + k + 1]) : false;
-#pragma unroll
-        for (int k = 0; k < 16; ++k) {
-            const int t = b0 + k;
-            if (t >= AMAX) break;
-            float ul_next = 0.0f;
-            if (t + 1 < AMAX) {
-                const bool tn1 = TN && ((u32)(uint8_t)a.adapter[t + 1] == (u32)'N');
-                const float pv = eq[k] ? pair_eq : pair_ne;
-                ul_next = S[t] + (tn1 ? pair_tn : pv);
-            }
-            float left = SM ? Sm[SM ? t : 0] : S[t] + -5.0f;
-            if (EARLY && t > 3) left = (t - 3 > q) ? -100000.0f : left;
-            const float sc = fmaxf(fmaxf(ul, uSm), left);
-            const float scm = sc + -5.0f;
-            S[t] = sc;
-            if (SM) Sm[SM ? t : 0] = scm;
-            uSm = scm; ul = ul_next;
-            if (t < AMIN) rowmax = fmaxf(rowmax, sc);
-            else rowmax = (t < A) ? fmaxf(rowmax, sc) : rowmax;
-        }
-    }
-    return rowmax;
-}
-
-#ifdef FXG_CLIP_DEBUG
-#define FXG_CLIP_DBG_WORDS 512u   // per read: [0,16) scalars and hashes, [16,272) level 3: (hash S, hash W) after each summary row, [272,464): S at r0, S and W before the last row
-#define FXG_CLIP_DBG(i, v) do { if (dbg) dbg[i] = (u32)(v); } while (0)
-FXG_HD u32 fxg_fbits(float f) { union { float f; u32 u; } x; x.f = f; return x.u; }
-template <int N> FXG_HD u32 fxg_dbg_hash(const float (&S)[N]) { u32 h = 0; for (int t = 0; t < N; ++t) h = h * 31u + fxg_fbits(S[t]); return h; }
-template <int N> FXG_HD u32 fxg_dbg_hash(const u32 (&W)[N]) { u32 h = 0; for (int t = 0; t < N; ++t) h = h * 31u + W[t]; return h; }
-#else
-FXG_HD u32 fxg_fbits(float) { return 0u; }
-#define FXG_CLIP_DBG(i, v) do { } while (0)
-#endif
 // returns r0 (the row the `start` field of bw counts from)
-template <int AMAX, bool TN, bool GL = false>      // GL: as in fxg_clip_two_pass
-FXG_HD int fxg_clip_two_pass_k(const FxgKArgs &a, const uint8_t *rd, int len, int rows, float *ck, u32 cks, float &best, u32 &bw, u32 &bq, int &first_n, u32 *dbg = nullptr, const bool UR = false,
+template <int AMAX, bool GL = false>      // GL: as in fxg_clip_two_pass
+FXG_HD int fxg_clip_two_pass_k(const FxgKArgs &a, const uint8_t *rd, int len, int rows, float *ck, u32 cks, float &best, u32 &bw, u32 &bq, int &first_n, const bool UR = false,
                                const uint8_t *ptab = nullptr)
 {
-    (void)dbg;
     float S[AMAX], Sm[AMAX];
     const int A = a.alen, K = (int)a.clip_ck_rows;
     const int early_rows = (A - 4 < rows) ? (A - 4 > 0 ? A - 4 : 0) : rows;
@@ -1130,7 +808,7 @@ FXG_HD int fxg_clip_two_pass_k(const FxgKArgs &a, const uint8_t *rd, int len, in
             if ((q & 3) == 3) { gw0 = gw1; gw1 = fxg_ld32(rd, (q >> 2) + 2, gmax); }                                         \
         } else { c = cn; cn = rd[q + 1]; }                                                                                   \
         if (mine) {                                                                                                          \
-            const float rm = fxg_clip_row_score_k<AMAX, EARLY, TN>(a, A, c, q, S, Sm, ptab);                                 \
+            const float rm = fxg_clip_row_score_k<AMAX, EARLY>(a, A, c, q, S, Sm, ptab);                                     \
             const bool g = rm > b1;                                                                                          \
             b1 = g ? rm : b1; bq1 = g ? q : bq1;                                                                             \
         }                                                                                                                    \
@@ -1146,7 +824,6 @@ FXG_HD int fxg_clip_two_pass_k(const FxgKArgs &a, const uint8_t *rd, int len, in
     const int r0 = bq1 - span + 1 > 0 ? bq1 - span + 1 : 0;
     const int j0 = r0 / K;
     q = j0 * K;
-    FXG_CLIP_DBG(0, bq1); FXG_CLIP_DBG(1, fxg_fbits(b1)); FXG_CLIP_DBG(2, r0); FXG_CLIP_DBG(3, j0);
     {
         const float *from = ck + (size_t)(j0 > 0 ? j0 - 1 : 0) * AMAX * cks;
 #pragma unroll
@@ -1158,92 +835,54 @@ FXG_HD int fxg_clip_two_pass_k(const FxgKArgs &a, const uint8_t *rd, int len, in
     }
     // Every lane has its own rows here, so the loops keep ONE body each: the early form (which tests the row number itself) wherever a
     // row below A - 4 can occur -- the < clip_ck_rows rows of the score re-run and the first A - 4 rows of the summary window.
-#if defined(FXG_CLIP_DEBUG) && FXG_CLIP_DEBUG >= 2
-    FXG_CLIP_DBG(4, fxg_dbg_hash(S));
-#endif
     {
         const int n0 = r0 - q, n0u = fxg_wave_max(n0);      // < clip_ck_rows rows of scores up to the first summary row
 #pragma unroll 1
         for (int i = 0; i < n0u; ++i) {
             if (i >= n0) continue;
-            (void)fxg_clip_row_score_k<AMAX, true, TN>(a, A, (u32)rd[q], q, S, Sm, ptab);
+            (void)fxg_clip_row_score_k<AMAX, true>(a, A, (u32)rd[q], q, S, Sm, ptab);
             ++q;
         }
     }
-#if defined(FXG_CLIP_DEBUG) && FXG_CLIP_DEBUG >= 2
-    FXG_CLIP_DBG(5, fxg_dbg_hash(S));
-#endif
     u32 W[AMAX];
 #pragma unroll
     for (int t = 0; t < AMAX; ++t) W[t] = FXG_K_START(256 + t + 1) + FXG_K_SZ1;         // the cells above row 0 (r0 > 0: never on the best path)
     float (&Sk)[FxgClipK<AMAX>::NSM] = reinterpret_cast<float (&)[FxgClipK<AMAX>::NSM]>(Sm);    // the summary rows keep S - 5 only where registers allow
-#ifdef FXG_CLIP_DEBUG
-    constexpr int DT0 = AMAX > 64 ? AMAX - 64 : 0;          // the LAST 64 columns of the wide buckets
-    (void)DT0;
-#endif
-#if defined(FXG_CLIP_DEBUG) && FXG_CLIP_DEBUG >= 3
-    if (dbg) for (int t = DT0; t < AMAX; ++t) dbg[272 + t - DT0] = fxg_fbits(S[t]);
-#define FXG_CLIP_DBG_ROW() do { const int wr_ = q - r0; if (dbg && wr_ < 128) { dbg[16 + 2 * wr_] = fxg_dbg_hash(S); dbg[17 + 2 * wr_] = fxg_dbg_hash(W); } } while (0)
-#else
-#define FXG_CLIP_DBG_ROW() do { } while (0)
-#endif
     const int win = bq1 - r0, n1 = win < early_rows ? win : early_rows, n2 = win - n1;      // summary rows in the early form / in the other
     const int n1u = fxg_wave_max(n1), n2u = fxg_wave_max(n2);
 #pragma unroll 1
     for (int i = 0; i < n1u; ++i) {
         if (i >= n1) continue;
-        fxg_clip_row_k<AMAX, true, false, TN>(a, A, (u32)rd[q], q, (u32)(q - r0), S, Sk, W, best, bw, bq, ptab); FXG_CLIP_DBG_ROW();
+        fxg_clip_row_k<AMAX, true, false>(a, A, (u32)rd[q], q, (u32)(q - r0), S, Sk, W, best, bw, bq, ptab);
         ++q;
     }
 #pragma unroll 1
     for (int i = 0; i < n2u; ++i) {
         if (i >= n2) continue;
-        fxg_clip_row_k<AMAX, false, false, TN>(a, A, (u32)rd[q], q, (u32)(q - r0), S, Sk, W, best, bw, bq, ptab); FXG_CLIP_DBG_ROW();
+        fxg_clip_row_k<AMAX, false, false>(a, A, (u32)rd[q], q, (u32)(q - r0), S, Sk, W, best, bw, bq, ptab);
         ++q;
     }
-#if defined(FXG_CLIP_DEBUG) && FXG_CLIP_DEBUG >= 3
-    if (dbg) for (int t = DT0; t < AMAX; ++t) { dbg[336 + t - DT0] = fxg_fbits(S[t]); dbg[400 + t - DT0] = W[t]; }
-#endif
-#ifdef FXG_CLIP_DEBUG_W      // lighter probes (the level-3 build no longer failed): only W / only a window of W before the last row
-    if (dbg) for (int t = (FXG_CLIP_DEBUG_W); t < AMAX && t < 64; ++t) dbg[400 + t] = W[t];
-#endif
-#ifdef FXG_CLIP_DEBUG_S
-    if (dbg) for (int t = (FXG_CLIP_DEBUG_S); t < AMAX && t < 64; ++t) dbg[336 + t] = fxg_fbits(S[t]);
-#endif
-#if defined(FXG_CLIP_DEBUG) && FXG_CLIP_DEBUG >= 2
-    FXG_CLIP_DBG(10, fxg_dbg_hash(S)); FXG_CLIP_DBG(11, fxg_dbg_hash(W));
-#endif
-    fxg_clip_row_k<AMAX, true, true, TN>(a, A, (u32)rd[bq1], bq1, (u32)(bq1 - r0), S, Sk, W, best, bw, bq, ptab);
-    FXG_CLIP_DBG(6, fxg_fbits(best)); FXG_CLIP_DBG(7, bw); FXG_CLIP_DBG(8, bq);
-#if defined(FXG_CLIP_DEBUG) && FXG_CLIP_DEBUG >= 2
-    FXG_CLIP_DBG(12, fxg_dbg_hash(S)); FXG_CLIP_DBG(13, fxg_dbg_hash(W));
-#endif
+    fxg_clip_row_k<AMAX, true, true>(a, A, (u32)rd[bq1], bq1, (u32)(bq1 - r0), S, Sk, W, best, bw, bq, ptab);
     if (!(a.clip_flags & FXG_CLIP_KEEP_N)) {                                             // the -n rule needs the first N of the read itself
         first_n = fxg_clip_first_n(rd, len, UR ? len : fxg_wave_max(len), a.clip_stride, first_n);
     }
     return r0;
 }
 
-// KFORM: the one-word summary of fxg_clip_row_k (17..99 columns; also 16 columns for reads beyond 255 bases, which the register
-// form of fxg_clip_two_pass cannot describe: its start field is absolute)
-template <int AMAX, bool KFORM, bool TN = false, bool GL = false>
+// KFORM: the one-word summary of fxg_clip_row_k (17..99 columns)
+template <int AMAX, bool KFORM, bool GL = false>
 FXG_HD void fxg_clip_read_packed(const FxgKArgs &a, const uint8_t *rd, int len, int rows,
-                                 u32 *out_len, u32 *keep, u32 *reason, u32 *clipped, u32 *adapter_only, float *ck = nullptr, u32 cks = 0u, u32 *dbg = nullptr, const bool UR = false,
+                                 u32 *out_len, u32 *keep, u32 *reason, u32 *clipped, u32 *adapter_only, float *ck = nullptr, u32 cks = 0u, const bool UR = false,
                                  const uint8_t *ptab = nullptr)
 {
-    (void)dbg; (void)ptab;
     float best = -1000000.0f;
     u32 bw = FXG_INVALID_TUPLE, bq = 0u;
     int first_n = len, qbase = 0;
-#ifndef FXG_CLIP_ONE_PASS
     if constexpr (!KFORM) qbase = fxg_clip_two_pass<AMAX, GL>(a, rd, len, rows, best, bw, bq, first_n, UR, ptab);
-    else
-#endif
-    if constexpr (!KFORM) fxg_clip_rows_packed<AMAX, false>(a, rd, len, rows, best, bw, bq, first_n, UR);
     if constexpr (KFORM) {
         int r0 = 0;
-        if (ck) r0 = fxg_clip_two_pass_k<AMAX, TN, GL>(a, rd, len, rows, ck, cks, best, bw, bq, first_n, dbg, UR, ptab);
-        else fxg_clip_rows_k<AMAX, TN>(a, rd, len, rows, best, bw, bq, first_n, UR, ptab);
+        if (ck) r0 = fxg_clip_two_pass_k<AMAX, GL>(a, rd, len, rows, ck, cks, best, bw, bq, first_n, UR, ptab);
+        else fxg_clip_rows_k<AMAX>(a, rd, len, rows, best, bw, bq, first_n, UR, ptab);
         const int v = (int)(bw >> 23), matches = (int)(bw & 127u), diag = (int)((bw >> 7) & 127u);
         fxg_clip_finish(a, len, v < 256 ? r0 + v : 0, v < 256 ? 0 : v - 256, diag - matches, (int)((bw >> 14) & 511u), matches,
                         (int)bq, first_n, out_len, keep, reason, clipped, adapter_only);
@@ -1366,11 +1005,9 @@ FXG_HD void fxg_phase_stage_bases(const uint8_t *src, u64 total, u64 tb, u32 tby
 }
 
 // phase 2, group A: thread tid decides read r0 + tid
-// AMAX > 0: general clipper (fallback, FXG_NO_PACKED_CLIP); AMAX < 0: packed clipper with bucket -AMAX columns (-216: 16 columns in the form of the 17..99 buckets, ablation build only)
-//   -(300 + columns): the same form for adapters that contain 'N' (buckets 16 24 36 48 64 100)
-__host__ __device__ constexpr int fxg_clip_cols(int amax) { return amax <= -300 ? -amax - 300 : amax <= -200 ? -amax - 200 : -amax; }
+// AMAX > 0: general clipper (fallback, FXG_NO_PACKED_CLIP); AMAX < 0: packed clipper with bucket -AMAX columns
+__host__ __device__ constexpr int fxg_clip_cols(int amax) { return -amax; }
 __host__ __device__ constexpr bool fxg_clip_kform(int amax) { return amax < -16; }
-__host__ __device__ constexpr bool fxg_clip_tn(int amax) { return amax <= -300; }
 // GL (two-pass forms only): the DP reads the batch in global memory, nothing was staged (sb unused)
 template <int AMAX, bool GL = false>
 FXG_HD u32 fxg_decide_a(const FxgKArgs &a, const u32 *bm_g, const u32 *bm_l, const uint8_t *sb, u32 r0, u32 tid,
@@ -1384,15 +1021,10 @@ FXG_HD u32 fxg_decide_a(const FxgKArgs &a, const u32 *bm_g, const u32 *bm_l, con
     if constexpr (AMAX < 0) {
         // fixed-length batch without clip history: the row count is a scalar, so every loop of the DP is a scalar loop
         constexpr int COLS = fxg_clip_cols(AMAX);
-        constexpr bool KF = fxg_clip_kform(AMAX), TN = fxg_clip_tn(AMAX);
-#ifdef FXG_CLIP_DEBUG
-        u32 *dbg = a.clip_dbg ? a.clip_dbg + (size_t)(r0 + tid) * FXG_CLIP_DBG_WORDS : nullptr;
-#else
-        u32 *dbg = nullptr;
-#endif
+        constexpr bool KF = fxg_clip_kform(AMAX);
         const uint8_t *rd = GL ? a.clip_src + (u64)(r0 + tid) * a.clip_stride : sb + tid * a.clip_stride;
-        if (!a.len && !a.wlen) fxg_clip_read_packed<COLS, KF, TN, GL>(a, rd, (int)a.fixed_len, (int)a.fixed_len, &curlen, &keep, &reason, &clipped, &ao, ck, cks, dbg, true, ptab);
-        else fxg_clip_read_packed<COLS, KF, TN, GL>(a, rd, (int)rl, rows, &curlen, &keep, &reason, &clipped, &ao, ck, cks, dbg, false, ptab);
+        if (!a.len && !a.wlen) fxg_clip_read_packed<COLS, KF, GL>(a, rd, (int)a.fixed_len, (int)a.fixed_len, &curlen, &keep, &reason, &clipped, &ao, ck, cks, true, ptab);
+        else fxg_clip_read_packed<COLS, KF, GL>(a, rd, (int)rl, rows, &curlen, &keep, &reason, &clipped, &ao, ck, cks, false, ptab);
     }
     if (keep && (a.stages & FXG_STAGE_QTRIM)) {             // fastq_quality_trimmer.c:94-101
         const u32 k = fxg_bits_last(bm_g, tid * stride, curlen);

@@ -107,19 +107,13 @@ static inline int fxg_make_plan(const fxg_batch *in, const fxg_params *p, const 
     if ((st & FXG_STAGE_FTRIM) && p->ft_first < 1) FXG_PLAN_FAIL("-f must be >= 1");
     pl->amax = !pl->clip ? 0 : ka.alen <= 16 ? 16 : ka.alen <= 32 ? 32 : ka.alen <= 64 ? 64 : 100;
     // Packed path summary (one u32 per cell); buckets are fine-grained because every padded column costs a full cell.
-    //   up to 16 columns, no 'N' in the adapter: two passes in registers (fxg_clip_two_pass), reads of any length (the start of a path
-    //   is recorded relative to the second pass' first row);
-    //   everything else: the form with ONE start field (fxg_clip_row_k) -- 17..99 columns, adapters that contain 'N' (instances
-    //   -(300 + columns), two more instructions per cell).
+    //   up to 16 columns: two passes in registers (fxg_clip_two_pass), reads of any length (the start of a path is recorded relative to
+    //   the second pass' first summary row);
+    //   17..99 columns: the form with ONE start field (fxg_clip_row_k).
     // That form runs two passes with its checkpoints in global scratch once the read is long enough to pay for the second one (one pass
     // ~15 VALU instructions per cell; two: ~6.5 + the <= SPAN + clip_ck_rows rows of the second pass), and always beyond 255 bases.
-#ifdef FXG_CLIP_ONE_PASS
-    const bool reg_any_len = false;              // (ablation build: the register form in one pass records absolute rows, 8 bits)
-#else
-    const bool reg_any_len = true;
-#endif
-    // (an 'N' in the adapter is one more column pattern of the pair table: the register form serves it like any other adapter)
-    const bool kform = pl->clip && (ka.alen > 16 || (ka.adapter_has_n && !fxg_clip_uses_ptab(-16)) || (ka.clip_stride > 255u && !reg_any_len));
+    // (an 'N' in the adapter is one more column pattern of the pair table: every form serves it like any other adapter)
+    const bool kform = pl->clip && ka.alen > 16;
     // Two passes pay while the summary rows of the second one (at most SPAN = A + (A + 1) / 5 rows up to the best row, plus the scores re-run from the last
     // checkpoint: < clip_ck_rows) are fewer than the read's rows: a score row is ~5 VALU instructions per cell with the pair table, a summary row ~10, and the
     // one-pass form tracks the best cell in every row (~15).  (Round 5: from 20 + 2 A bases on -- its score rows cost 7 per cell and a 44-column adapter on
@@ -130,29 +124,22 @@ static inline int fxg_make_plan(const fxg_batch *in, const fxg_params *p, const 
     const bool two_pass_k = kform && (span_k + ka.clip_ck_rows + ka.clip_stride / 10u <= ka.clip_stride || ka.clip_stride > 255u) && !getenv("FXG_CLIP_K_ONE_PASS");
     pl->ck_per_wg = 0;
     ka.clip_ck = nullptr;
-    if (pl->clip && (ka.clip_stride <= 255u || two_pass_k || (!kform && reg_any_len)) && !getenv("FXG_NO_PACKED_CLIP")) {
+    if (pl->clip && (ka.clip_stride <= 255u || two_pass_k || !kform) && !getenv("FXG_NO_PACKED_CLIP")) {
         // 36: the 33/34-base TruSeq adapters; 56 and 80 (round 5): 49..56 columns no longer pay for 64 (17.4 -> 27.7 ms between 48 and 49 bases,
         // profiles/r04/p_clip_waves_by_adapter_len.txt) and 65..80 no longer for 100
         // 44, 52, 60, 72, 88 (round 6): a bucket every 4 columns to 64 and every 8 to 88, so that no adapter pays for more than 8 % .. 12 % of padding columns
         static const int pk[] = {4, 8, 9, 10, 11, 12, 13, 14, 15, 16, 20, 24, 28, 32, 36, 40, 44, 48, 52, 56, 60, 64, 72, 80, 88, 100};
-        static const int pn[] = {16, 24, 36, 48, 56, 64, 80, 100};
         int b = 100;
-        const bool n_inst = ka.adapter_has_n && kform && !fxg_clip_uses_ptab(-20);      // (builds without the pair table: the instances with per-column neutral selects)
-        if (n_inst) { for (unsigned i = 0; i < sizeof pn / sizeof pn[0]; ++i) if (ka.alen <= pn[i]) { b = pn[i]; break; } }
-        else { for (unsigned i = 0; i < sizeof pk / sizeof pk[0]; ++i) if (ka.alen <= pk[i]) { b = pk[i]; break; } }
-        if (b < 16 && kform) b = 16;
-        pl->amax = n_inst ? -(300 + b) : (b == 16 && kform) ? -216 : -b;
+        for (unsigned i = 0; i < sizeof pk / sizeof pk[0]; ++i) if (ka.alen <= pk[i]) { b = pk[i]; break; }
+        pl->amax = -b;
         if (two_pass_k) pl->ck_per_wg = (u64)FXG_CK_SLOTS * (u64)b * FXG_TBLOCK;
         // the pair table of the instance (fxg_kernels.h: fxg_clip_ptab_build): as many columns as the bucket, rounded up to whole 16-byte blocks
-        if (fxg_clip_uses_ptab(pl->amax)) {
-            const bool kf = fxg_clip_kform(pl->amax);
-            ka.clip_ptab_cols = kf ? ((u32)b + 3u) & ~3u : 16u;
-            ka.clip_ptab_stride = fxg_ptab_stride(ka.clip_ptab_cols);
-            ka.clip_ptab_dia1 = kf ? FXG_K_DIA1 : FXG_PK_DIA1;
-            if (kf && ka.clip_ptab_rows > FXG_PTAB_MAX_ROWS_K) {      // an adapter of more than six distinct bytes and more than 16 columns: the general form
-                pl->amax = ka.alen <= 32 ? 32 : ka.alen <= 64 ? 64 : 100;
-                pl->ck_per_wg = 0;
-            }
+        ka.clip_ptab_cols = kform ? ((u32)b + 3u) & ~3u : 16u;
+        ka.clip_ptab_stride = fxg_ptab_stride(ka.clip_ptab_cols);
+        ka.clip_ptab_dia1 = kform ? FXG_K_DIA1 : FXG_PK_DIA1;
+        if (kform && ka.clip_ptab_rows > FXG_PTAB_MAX_ROWS_K) {      // an adapter of more than six distinct bytes and more than 16 columns: the general form
+            pl->amax = ka.alen <= 32 ? 32 : ka.alen <= 64 ? 64 : 100;
+            pl->ck_per_wg = 0;
         }
     }
     // quality trim / filter with compaction over rows of 80..152 bytes: one lane per read, 64 reads per tile (fxg_rows.h).  Shorter
@@ -187,7 +174,6 @@ static inline int fxg_make_plan(const fxg_batch *in, const fxg_params *p, const 
     // boundaries; runs with clip history (ragged input of the tools) keep the staged form.  FXG_CLIP_GLOBAL=0 / 1 overrides (tests run both).
     ka.clip_global = 0u;
     u32 T = pl->rows_nw ? 64u * (u32)pl->rows_r / (u32)pl->rows_h : fxg_pick_tile(pl->clip ? ka.clip_stride : in->stride, pl->clip, pl->block);
-#ifndef FXG_CLIP_ONE_PASS
     if (pl->clip && pl->amax < 0 && (pl->amax >= -16 || pl->ck_per_wg != 0) && clip_stride == 0u && (ka.clip_stride & 3u) == 0u && ((uintptr_t)ka.clip_src & 3u) == 0u) {      // (clip_stride != 0: a run with clip history, whose rows are settled after the plan)
         ka.tile_reads = T; ka.depth = 2u;
         const bool cramped = T < pl->block || (156u * 1024u) / fxg_plan_lds(pl) < 3u;
@@ -195,7 +181,6 @@ static inline int fxg_make_plan(const fxg_batch *in, const fxg_params *p, const 
         ka.clip_global = (e ? atoi(e) != 0 : cramped) ? 1u : 0u;
         if (ka.clip_global) T = pl->block;
     }
-#endif
     const u64 ntiles = (in->n + T - 1) / T;
     if (ntiles > 0x7FFFFFFFull || in->n > 0xFFFFFFFFull) FXG_PLAN_FAIL("batch too large (%llu reads): split it", (unsigned long long)in->n);
     ka.tile_reads = T; ka.ntiles = (u32)ntiles;

@@ -337,16 +337,14 @@ __device__ __forceinline__ void fxg_rows_flush(uint8_t *out, u64 base, u32 totb,
     uint8_t *g0 = out + (base - sh);
     const u32 first = sh ? 1u : 0u, end = (sh + totb) >> 4;      // whole units: first <= i < end
     const u32 s2 = (16u - sh) & 15u, qd = s2 >> 2, r = s2 & 3u;  // unit i starts at packed byte 16 i - sh = 16 (i - first) + s2
-#if FXG_STORE_GRID
     // lane l takes the units whose place in their 128-byte line is l mod 8: every store instruction of the wave then covers eight whole lines of the output
-    // (the first one starts at most seven lanes short) instead of straddling nine: cfg2 4.08 -> 4.03 ms, mean of four alternating runs (profiles/r06/store_grid_cfg2.txt)
+    // (the first one starts at most seven lanes short) instead of straddling nine: cfg2 4.08 -> 4.03 ms against unit i on lane i, mean of four alternating
+    // runs (profiles/r06/store_grid_cfg2.txt).  The tile kernels' gather was measured the same way and lost 1.6-3 % (cfg4, cfg3, cfg5:
+    // profiles/r06/store_grid_other.txt): it keeps chunk ci on lane ci.
     const int a8 = (int)(((base - sh) >> 4) & 7u);
     for (int ii = (int)lane - a8; ii < (int)end; ii += 64) {
         if (ii < (int)first) continue;
         const u32 i = (u32)ii;
-#else
-    for (u32 i = first + lane; i < end; i += 64u) {
-#endif
         const u32x4 *src = reinterpret_cast<const u32x4 *>(obuf + ((i - first) << 4));
         const u32x4 v0 = src[0], v1 = src[1];
         u32 w0, w1, w2, w3, w4;

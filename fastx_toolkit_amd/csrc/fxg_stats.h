@@ -123,10 +123,6 @@ FXG_HD void fxg_stats_masks(u32 nb, u32 (&m)[4])
 // sl: strip of the block (LDS position); m: fxg_stats_masks(o.nb)
 FXG_HD void fxg_stats_accumulate(const FxgStatsArgs &a, const FxgStripRow &o, u32 sl, u32 col0, const u32 (&m)[4], u32 *lds)
 {
-#ifdef FXG_QS_NOACC        // timing experiment (wrong counts): the kernel's loads alone -- one LDS add per row keeps them alive
-    FXG_LDS_ADD(lds + (threadIdx.x & 63u), o.vb.x ^ o.vb.y ^ o.vb.z ^ o.vb.w ^ o.vq.x ^ o.vq.y ^ o.vq.z ^ o.vq.w);
-    return;
-#endif
     if (o.nb == 0u) return;
     u32 wb[4] = {o.vb.x, o.vb.y, o.vb.z, o.vb.w}, wq[4] = {o.vq.x, o.vq.y, o.vq.z, o.vq.w};
     // Fast path: 16 bases A C G T N (either case) whose quality bytes all lie in the window -- no per-base test, no branch.
@@ -153,13 +149,8 @@ FXG_HD void fxg_stats_accumulate(const FxgStatsArgs &a, const FxgStripRow &o, u3
             // halves of h: class << 8 | offset of base j (low) and of base j + 1 (high) = byte offset inside the pair's block
             const u32 h = fxg_perm(k4[j >> 2], o4[j >> 2], (j & 2u) ? 0x07030602u : 0x05010400u);
             unsigned char *pb = base + (j >> 1) * (FXG_QS_LROWS * FXG_QS_LROW_WORDS * 4u);
-#ifdef FXG_QS_FAKE_BANKS      // timing experiment (wrong counts): every lane of a wave on its own bank -- what the kernel would take without LDS bank conflicts
-            FXG_LDS_ADD(reinterpret_cast<u32 *>(pb + ((h & 0xFF00u) | ((threadIdx.x & 63u) << 2))), 1u);
-            FXG_LDS_ADD(reinterpret_cast<u32 *>(pb + (((h >> 16) & 0xFF00u) | ((threadIdx.x & 63u) << 2))), 0x10000u);
-#else
             FXG_LDS_ADD(reinterpret_cast<u32 *>(pb + (h & 0xFFFFu)), 1u);
             FXG_LDS_ADD(reinterpret_cast<u32 *>(pb + (h >> 16)), 0x10000u);
-#endif
         }
         return;
     }
@@ -237,10 +228,6 @@ FXG_HD void fxg_stats_piece_lane(u32 L, u32 o, FxgPieceLane<ODD> &c)     // o: c
 template <bool ODD>
 FXG_HD void fxg_stats_accumulate_piece(const FxgStatsArgs &a, const FxgStripRow &r, const FxgPieceLane<ODD> &c, u32 *lds)
 {
-#ifdef FXG_QS_NOACC
-    FXG_LDS_ADD(lds + (threadIdx.x & 63u), r.vb.x ^ r.vb.y ^ r.vb.z ^ r.vb.w ^ r.vq.x ^ r.vq.y ^ r.vq.z ^ r.vq.w);
-    return;
-#endif
     const u32 wb[4] = {r.vb.x, r.vb.y, r.vb.z, r.vb.w}, wq[4] = {r.vq.x, r.vq.y, r.vq.z, r.vq.w};
     u32 bad = 0u, k4[4], o4[4];
 #pragma unroll
@@ -297,9 +284,6 @@ FXG_HD void fxg_stats_slice(const FxgStatsArgs &a, u32 g, u64 *lo, u64 *hi)
 // three or four times per kernel, with every workgroup of the chip at the barrier at the same time.)
 FXG_HD void fxg_stats_flush(u32 *lds, u32 *part, u32 t, u32 nt, bool first)
 {
-#ifdef FXG_QS_NOFLUSH     // timing experiment (wrong counts): what the kernel takes without the flushes' traffic
-    if (!first) return;
-#endif
     for (u32 i = t; i < FXG_QS_LDS_WORDS; i += nt) {
         const u32 x = i % FXG_QS_LROW_WORDS, pk = i / FXG_QS_LROW_WORDS, k = pk % FXG_QS_LROWS, pair = pk / FXG_QS_LROWS;
         const u32 v = lds[i];
@@ -338,23 +322,14 @@ FXG_HD void fxg_stats_item(u64 lo, u64 g, u64 *r, u32 *sl) { *r = lo + g / FXG_Q
 // Cache policy of the loop's row loads.  ROW-STRIP form: the DEFAULT policy.  With the non-temporal policy it is 1.0-1.7 % faster (2.667 against 2.713 ms, mean of
 // eight alternating runs, profiles/r06/stats_nt_loads.txt; 2.724 against 2.751, stats_variants_one_call.txt) but fetches 7 % more: the 16-byte pieces of 150-byte
 // rows share their first and last 128-byte lines with the neighbouring wave's, and a line marked non-temporal is gone before the neighbour asks (FETCH_SIZE
-// 1.05 -> 1.12 x the rows, profiles/r06_pmc_stats).  Bytes over the fabric are the scarcer thing; -DFXG_QS_NTL builds the other arm.
+// 1.05 -> 1.12 x the rows, profiles/r06_pmc_stats).  Bytes over the fabric are the scarcer thing.
 // PIECE form: NON-TEMPORAL.  Its waves load whole lines that no other wave touches, so the policy costs no byte (FETCH_SIZE 1.024 x the rows either way) and the
 // kernel takes 2.42-2.44 instead of 2.52-2.54 ms, four alternating runs (profiles/r06/stats_piece_nt_depth.txt, stats_piece_nt_traffic.txt; loads 2 or 4 trips
-// ahead instead of 3: no difference, same file); -DFXG_QS_PIECE_DEFAULT_LOADS builds the other arm.
+// ahead instead of 3: no difference, same file).
 struct FxgLdDefault {};
 struct FxgLdStream {};
 __device__ __forceinline__ u32x4 fxg_qs_ld(const uint8_t *p, FxgLdStream) { return __builtin_nontemporal_load(reinterpret_cast<const u32x4_unaligned *>(p)); }
-#ifdef FXG_QS_NTL
-__device__ __forceinline__ u32x4 fxg_qs_ld(const uint8_t *p, FxgLdDefault) { return __builtin_nontemporal_load(reinterpret_cast<const u32x4_unaligned *>(p)); }
-#else
 __device__ __forceinline__ u32x4 fxg_qs_ld(const uint8_t *p, FxgLdDefault) { return fxg_ld16(p); }
-#endif
-#ifdef FXG_QS_PIECE_DEFAULT_LOADS
-typedef FxgLdDefault FxgLdPiece;
-#else
-typedef FxgLdStream FxgLdPiece;
-#endif
 // Fixed-length batches with qualities: trip T of the launch is reads [96 T, 96 T + 96) and belongs to workgroup T mod G, so that at any moment the whole chip
 // reads ONE narrow window of each array (256 x 14 KB) -- the order the memory system serves best: a read-only stream of 15 GB takes 2.33 ms that way
 // (2.20 with the non-temporal policy) against 2.45-2.50 ms from one far-apart slice per workgroup (scripts/ubench/read_stream.hip, profiles/r06/
@@ -369,9 +344,6 @@ __device__ __forceinline__ void fxg_quality_stats_body(const FxgStatsArgs &a)
 {
     extern __shared__ __attribute__((aligned(16))) u32 qs_h[];
     const u32 tid = threadIdx.x;
-#ifdef FXG_QS_CLOCKS      // measurement build: when each workgroup of the launch started, left its loop and ended (100 MHz ticks), left in unused bins of the result
-    const u64 qs_t0 = __builtin_amdgcn_s_memrealtime();
-#endif
     u32 *part = a.partial + (u64)blockIdx.x * FXG_QS_PART_WORDS;
     for (u32 i = tid; i < FXG_QS_LDS_WORDS; i += FXG_QS_TBLOCK) qs_h[i] = 0u;
     const bool dealt = !a.len && a.qual && a.round_robin != 0u;
@@ -480,8 +452,8 @@ __device__ __forceinline__ void fxg_quality_stats_body(const FxgStatsArgs &a)
                 const bool mine = tid < Pn, mine_last = tid < Pl;
                 auto pieces = [&](auto &pc) {
                     fxg_stats_piece_lane(a.fixed_len, o, pc);
-                    run(cnt - (owns_last ? 1u : 0u), [&](const FxgStripRow &row) { if (mine) fxg_stats_accumulate_piece(a, row, pc, qs_h); }, FxgLdPiece{});
-                    if (owns_last) run(1u, [&](const FxgStripRow &row) { if (mine_last) fxg_stats_accumulate_piece(a, row, pc, qs_h); }, FxgLdPiece{});
+                    run(cnt - (owns_last ? 1u : 0u), [&](const FxgStripRow &row) { if (mine) fxg_stats_accumulate_piece(a, row, pc, qs_h); }, FxgLdStream{});
+                    if (owns_last) run(1u, [&](const FxgStripRow &row) { if (mine_last) fxg_stats_accumulate_piece(a, row, pc, qs_h); }, FxgLdStream{});
                 };
                 FxgPieceLane<ODDK> pc;
                 pieces(pc);
@@ -489,16 +461,7 @@ __device__ __forceinline__ void fxg_quality_stats_body(const FxgStatsArgs &a)
         }
     }
     __syncthreads();
-#ifdef FXG_QS_CLOCKS
-    const u64 qs_t1 = __builtin_amdgcn_s_memrealtime();
-#endif
     fxg_stats_flush(qs_h, part, tid, FXG_QS_TBLOCK, nflush++ == 0u);
-#ifdef FXG_QS_CLOCKS
-    if (tid == 0) {      // into bins 0..2 of (column g / 5, class g % 5): no quality byte of the measurement's input lands there
-        u64 *o = a.hist + ((u64)(blockIdx.x / 5u) * FXG_QS_CLASSES + blockIdx.x % 5u) * FXG_QS_BINS;
-        o[0] = qs_t0; o[1] = qs_t1; o[2] = __builtin_amdgcn_s_memrealtime();
-    }
-#endif
 }
 
 __global__ __launch_bounds__(FXG_QS_TBLOCK) void fxg_kernel_quality_stats(const FxgStatsArgs a) { fxg_quality_stats_body<false>(a); }

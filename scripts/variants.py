@@ -15,9 +15,7 @@ from fastx_toolkit_amd import build as _b  # noqa: E402
 
 VARIANTS = {            # edit freely: every entry becomes fastx_toolkit_amd/libfxg_v_<name>.so
     "abl": ["-DFXG_ABLATION"],
-    "abl_nonts": ["-DFXG_ABLATION", "-DFXG_V_NO_NTS"],
     "abl_ldnt": ["-DFXG_ABLATION", "-DFXG_ROWS_LD_AUX=2"],
-    "abl_ldnt_nonts": ["-DFXG_ABLATION", "-DFXG_ROWS_LD_AUX=2", "-DFXG_V_NO_NTS"],
     "full_bases": ["-DFXG_ROWS_SPARSE_BASES=0"],       # the rows kernels' stage B fetches every base row whole (before the sparse fetch)
     "sparse_multi": ["-DFXG_ROWS_SPARSE_BASES=2"],     # the sparse base fetch in fxg_kernel_rows_multi too
 }

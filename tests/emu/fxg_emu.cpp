@@ -168,9 +168,6 @@ int emu_clip_group1(const FxgPlan &pl, uint64_t *ctr, char *err, size_t cap)
     case 16: return emu_run<16, false>(pl, ctr, err, cap);
     case 32: return emu_run<32, false>(pl, ctr, err, cap);
     case 64: return emu_run<64, false>(pl, ctr, err, cap);
-#ifdef FXG_CLIP_ONE_PASS
-    case -216: return emu_run<-216, false>(pl, ctr, err, cap);
-#endif
     default: return EMU_NOT_MINE;
     }
 }
@@ -300,10 +297,6 @@ static int g_last_amax, g_last_two_pass, g_last_clip_global, g_last_tile;
 extern "C" void fxg_emu_last_plan(int *amax, int *two_pass) { *amax = g_last_amax; *two_pass = g_last_two_pass; }
 extern "C" void fxg_emu_last_plan_clip_global(int *on, int *tile_reads) { *on = g_last_clip_global; *tile_reads = g_last_tile; }
 
-#ifdef FXG_CLIP_DEBUG
-static std::vector<u32> g_clip_dbg;
-extern "C" size_t fxg_emu_clip_debug(u32 *out, size_t cap_words) { const size_t k = g_clip_dbg.size() < cap_words ? g_clip_dbg.size() : cap_words; memcpy(out, g_clip_dbg.data(), k * 4); return k; }
-#endif
 extern "C" int fxg_emu_run_pipeline_hist(const fxg_batch *in, const fxg_params *p, const fxg_out *out, char *err, size_t cap, fxg_emu_hist *hs)
 {
     FxgPlan pl;
@@ -313,10 +306,6 @@ extern "C" int fxg_emu_run_pipeline_hist(const fxg_batch *in, const fxg_params *
     if (rc != FXG_OK) return rc;
     g_last_amax = pl.amax; g_last_two_pass = pl.ck_per_wg != 0; g_last_clip_global = (int)pl.ka.clip_global; g_last_tile = (int)pl.ka.tile_reads;
     if (in->n == 0) return FXG_OK;
-#ifdef FXG_CLIP_DEBUG      // debug builds (scripts/debug/clip64_bisect.py): the per-read dump of fxg_clip_two_pass_k, read back through fxg_emu_clip_debug
-    g_clip_dbg.assign((size_t)in->n * FXG_CLIP_DBG_WORDS, 0xEEEEEEEEu);
-    pl.ka.clip_dbg = g_clip_dbg.data();
-#endif
     if (hist) {
         int use = 0;
         emu_hist_prepass(hs, in, pl.ka.tile_reads, estride, &pl.ka, &use);

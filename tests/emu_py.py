@@ -46,7 +46,7 @@ def _emu_objects(defs):
 
 
 def build():
-    defs = os.environ.get("FXG_EMU_DEFS", "").split()           # e.g. "-DFXG_V_TABLE": check a kernel variant on the CPU tier
+    defs = os.environ.get("FXG_EMU_DEFS", "").split()           # e.g. "-DFXG_ROWS_SPARSE_BASES=0": check a kernel variant on the CPU tier
     so = os.path.join(_EMU, "libfxgemu%s.so" % "".join(d.replace("-D", "_") for d in defs))
     objs = _emu_objects(defs)
     if not os.path.exists(so) or os.path.getmtime(so) < max(os.path.getmtime(o) for o in objs):
