@@ -41,12 +41,13 @@ def check_exec_zero(so):
                            "Change the register budget of the named instance (fxg_clip_waves / __launch_bounds__) or its source and rebuild.\n%s" % (so, p.stdout[-3000:]))
 
 
-CLIP_UNITS = 7      # csrc/fxg_engine_clip.hip is compiled once per group of clip instances (-DFXG_CLIP_TU=1..7), beside csrc/fxg_engine.hip (-DFXG_SPLIT)
+CLIP_UNITS = 7      # csrc/fxg_engine_clip.hip is compiled once per unit of csrc/fxg_clip_instances.h (-DFXG_CLIP_TU=1..7), beside csrc/fxg_engine.hip (-DFXG_SPLIT);
+                    # a count that differs from the header's does not compile or link, and tests/test_clip_instances.py compares the two
 
 
 def compile_engine(out, extra_flags=(), check=True):
     """The engine into `out`, through a temporary name: a library that fails the ISA check never appears under `out`.  Eight translation units compiled
-    side by side (csrc/fxg_host.h: the clip instances are most of the work; as one unit the build took three and a half minutes), then one link."""
+    side by side (csrc/fxg_clip_instances.h: the clip instances are most of the work; as one unit the build took three and a half minutes), then one link."""
     tmp = out + ".new"
     objdir = os.path.join(ROOT, "build", "engine_" + os.path.basename(out).replace(".", "_"))
     os.makedirs(objdir, exist_ok=True)

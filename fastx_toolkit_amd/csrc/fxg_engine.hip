@@ -231,11 +231,19 @@ extern "C" int fxg_run_pipeline(fxg_ctx *c, const fxg_batch *in, const fxg_param
     return fxg_launch_plan(c, pl, (u64 *)out->counters);
 }
 
+// the clipper's instances live in translation units of their own (fxg_engine_clip.hip): the unit that holds the planned one launches it
+static int fxg_launch_clip(fxg_ctx *c, FxgPlan &pl, u64 *ctr)
+{
+    int rc;
+#define FXG_CLIP_TRY_UNIT(K) if ((rc = FXG_CLIP_UNIT_FN(K)(c, pl, ctr)) != FXG_CLIP_NOT_MINE) return rc;
+    FXG_CLIP_FOR_UNITS(FXG_CLIP_TRY_UNIT)
+#undef FXG_CLIP_TRY_UNIT
+    return fxg_fail(c, FXG_E_INVALID, "no clip instance %d", pl.amax);
+}
+
 // the launch of a planned pass: which instance of which kernel family
 static int fxg_launch_plan(fxg_ctx *c, FxgPlan &pl, u64 *ctr)
 {
-#define FXG_TILES_A(N) (fxg_kernel_tiles<N, 0>)
-#define FXG_TILES_C(N) (pl.ka.clip_global ? fxg_kernel_tiles<N, 0, true> : fxg_kernel_tiles<N, 0, false>)      // packed clip instances: the DP over the staged tile, or over the batch (fxg_plan.h)
     if (pl.rows_nw) {       // rows of 80..152 bytes through the quality stages: one lane per read, rows in registers (fxg_rows.h)
         if (pl.rows_h == 2) {     // rows of 153..304 bytes: two lanes per read
             if (pl.rows_nw == 26) return fxg_launch_tiles(c, fxg_kernel_rows<26, 2>, "fxg_kernel_rows<26,2> qtrim+qfilter", pl.ka, pl.lds, ctr, 64u, true);
@@ -250,16 +258,14 @@ static int fxg_launch_plan(fxg_ctx *c, FxgPlan &pl, u64 *ctr)
         }
     }
     if (pl.group_a) {
-        if (pl.amax == 0) return fxg_launch_tiles(c, FXG_TILES_A(0), "fxg_kernel_tiles<0,0> qtrim+qfilter", pl.ka, pl.lds, ctr);
-        // the clipper's instances live in translation units of their own (fxg_engine_clip.hip)
-        return pl.amax < -16 ? fxg_launch_clip_k(c, pl, ctr) : fxg_launch_clip_reg(c, pl, ctr);
+        if (pl.amax == 0) return fxg_launch_tiles(c, fxg_kernel_tiles<0, 0>, "fxg_kernel_tiles<0,0> qtrim+qfilter", pl.ka, pl.lds, ctr);
+        return fxg_launch_clip(c, pl, ctr);
     }
     if (pl.mask) return fxg_launch_tiles(c, fxg_kernel_tiles<0, 3>, "fxg_kernel_tiles<0,3> mask", pl.ka, pl.lds, ctr);
     if (pl.artifacts) return fxg_launch_tiles(c, fxg_kernel_tiles<0, 4>, "fxg_kernel_tiles<0,4> base census", pl.ka, pl.lds, ctr);
     if (pl.rev && pl.ka.rev_dw) return fxg_launch_tiles(c, fxg_kernel_tiles<0, 5>, "fxg_kernel_tiles<0,5> revcomp[+ftrim], dword-aligned windows", pl.ka, pl.lds, ctr);
     if (pl.rev) return fxg_launch_tiles(c, fxg_kernel_tiles<0, 2>, "fxg_kernel_tiles<0,2> revcomp[+ftrim]", pl.ka, pl.lds, ctr);
     return fxg_launch_tiles(c, fxg_kernel_tiles<0, 1>, "fxg_kernel_tiles<0,1> ftrim", pl.ka, pl.lds, ctr);
-#undef FXG_TILES_A
 }
 
 extern "C" int fxg_run_quality_stats(fxg_ctx *c, const fxg_batch *in, uint64_t *d_hist, uint32_t hist_cols)

@@ -1,9 +1,8 @@
 // fxg_host.h -- what the translation units of the engine share on the host side: the context, the error macros, the launch of one instance of a tile
-// kernel.  The engine is built from EIGHT translation units compiled side by side (fastx_toolkit_amd/build.py): fxg_engine.hip (every entry point of the
-// C-ABI and every kernel but the clipper's) and fxg_engine_clip.hip seven times (-DFXG_CLIP_TU=1: the register forms of up to 16 columns and the general
-// form; 2 / 4 / 6: 20..36 / 40, 48, 56 / 64, 80, 100 columns; 3 / 5 / 7: 44, 52 / 60, 72 / 88 columns) -- the clip instances are most of what hipcc spends its
-// time on, and one translation unit of 100 kernels took three and a half minutes.  Compiled alone (no -DFXG_SPLIT: the variant / matrix / ablation builds of scripts/) fxg_engine.hip includes
-// the clip file and is the one translation unit it used to be.
+// kernel.  The engine is built from several translation units compiled side by side (fastx_toolkit_amd/build.py): fxg_engine.hip (every entry point of the
+// C-ABI and every kernel but the clipper's) and fxg_engine_clip.hip once per unit of clip instances (-DFXG_CLIP_TU=k; fxg_clip_instances.h lists the units
+// and says why).  Compiled alone (no -DFXG_SPLIT: the variant / matrix / ablation builds of scripts/) fxg_engine.hip includes the clip file and is the one
+// translation unit it used to be.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -100,14 +99,12 @@ static int fxg_fail(fxg_ctx *ctx, int code, const char *fmt, ...)
 // the -v report counters of a launch: the tile kernel tallied them, one tiny kernel lays them out (defined with that kernel, in fxg_engine.hip)
 #define FXG_INTERNAL __attribute__((visibility("hidden")))      /* between the engine's translation units; not part of the C-ABI */
 FXG_INTERNAL int fxg_enqueue_finish_counters(fxg_ctx *c, const FxgKArgs &ka, u64 *counters);
-// the clip instances, by translation unit (fxg_engine_clip.hip)
-FXG_INTERNAL int fxg_launch_clip_reg(fxg_ctx *c, FxgPlan &pl, u64 *ctr);
-FXG_INTERNAL int fxg_launch_clip_k(fxg_ctx *c, FxgPlan &pl, u64 *ctr);
-FXG_INTERNAL int fxg_launch_clip_k_wide(fxg_ctx *c, FxgPlan &pl, u64 *ctr);
-FXG_INTERNAL int fxg_launch_clip_k_wide_wide(fxg_ctx *c, FxgPlan &pl, u64 *ctr);
-FXG_INTERNAL int fxg_launch_clip_k44_52(fxg_ctx *c, FxgPlan &pl, u64 *ctr);
-FXG_INTERNAL int fxg_launch_clip_k60_72(fxg_ctx *c, FxgPlan &pl, u64 *ctr);
-FXG_INTERNAL int fxg_launch_clip_k88(fxg_ctx *c, FxgPlan &pl, u64 *ctr);
+// the clip instances, one launch function per unit (fxg_engine_clip.hip): FXG_CLIP_NOT_MINE for a plan whose instance another unit holds
+#define FXG_CLIP_NOT_MINE 1
+#define FXG_CLIP_UNIT_FN_(K) fxg_launch_clip_unit##K
+#define FXG_CLIP_UNIT_FN(K) FXG_CLIP_UNIT_FN_(K)
+#define FXG_CLIP_DECLARE_UNIT(K) FXG_INTERNAL int FXG_CLIP_UNIT_FN(K)(fxg_ctx *c, FxgPlan &pl, u64 *ctr);
+FXG_CLIP_FOR_UNITS(FXG_CLIP_DECLARE_UNIT)
 
 // ------------------------------------------------------------------------------------------------
 

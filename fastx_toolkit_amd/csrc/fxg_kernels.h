@@ -16,6 +16,7 @@
 // fxg_kernel_finish_counters lays them out.  The clip instances write out two steps behind (three slots) where LDS allows.
 #pragma once
 #include "fxg_device.h"
+#include "fxg_clip_instances.h"
 
 #define FXG_INVALID_TUPLE 0xFFFFFFFFu
 
@@ -605,11 +606,10 @@ FXG_HD int fxg_clip_two_pass(const FxgKArgs &a, const uint8_t *rd, int len, int 
 #define FXG_K_DIA1 (1u << 7)
 #define FXG_K_SZ1  (1u << 14)
 #define FXG_K_START(v) ((u32)(v) << 23)
-// smallest adapter of the bucket AMAX (fxg_plan.h): columns below it always count towards the best cell
-__host__ __device__ constexpr int fxg_clip_k_amin(int amax)
-{
-    return amax <= 16 ? 1 : amax <= 20 ? 17 : amax <= 64 ? amax - 3 : amax <= 88 ? amax - 7 : 89;      // buckets every 4 columns to 64, every 8 to 88, then 100 (fxg_plan.h)
-}
+// smallest adapter of the bucket AMAX (fxg_clip_instances.h): columns below it always count towards the best cell
+__host__ __device__ constexpr int fxg_clip_k_amin(int amax) { return amax <= 16 ? 1 : fxg_clip_bucket_below(amax) + 1; }
+static_assert(fxg_clip_k_amin(16) == 1 && fxg_clip_k_amin(20) == 17 && fxg_clip_k_amin(24) == 21 && fxg_clip_k_amin(64) == 61 && fxg_clip_k_amin(72) == 65 &&
+              fxg_clip_k_amin(88) == 81 && fxg_clip_k_amin(100) == 89, "a bucket's smallest adapter is the next smaller bucket + 1");
 template <int AMAX> struct FxgClipK { static constexpr bool SM = AMAX <= 24; static constexpr int NSM = SM ? AMAX : 1; };
 
 // The rows of the 17..99-column forms take their pair values out of the pair table (round 6): block b of a table row holds the pair values of columns 4 b .. 4 b + 3, the step row

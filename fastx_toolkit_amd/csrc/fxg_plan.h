@@ -5,8 +5,11 @@
 #include <cstdlib>
 #include <cstring>
 
+#include "fxg_clip_instances.h"
 #include "fxg_kernels.h"
 #include "fxg_rows.h"
+
+static_assert(fxg_clip_bucket(1) != 0 && fxg_clip_bucket(FXG_MAX_ADAPTER) != 0, "every adapter length the plan accepts needs a packed clip instance");
 
 struct FxgPlan {
     FxgKArgs ka;
@@ -106,7 +109,7 @@ static inline int fxg_make_plan(const fxg_batch *in, const fxg_params *p, const 
     if (pl->clip && ka.clip_stride > 65000u) FXG_PLAN_FAIL("clip: reads longer than 65000 are not supported");
     if ((st & FXG_STAGE_FTRIM) && p->ft_first < 1) FXG_PLAN_FAIL("-f must be >= 1");
     pl->amax = !pl->clip ? 0 : ka.alen <= 16 ? 16 : ka.alen <= 32 ? 32 : ka.alen <= 64 ? 64 : 100;
-    // Packed path summary (one u32 per cell); buckets are fine-grained because every padded column costs a full cell.
+    // Packed path summary (one u32 per cell); the buckets: fxg_clip_instances.h.
     //   up to 16 columns: two passes in registers (fxg_clip_two_pass), reads of any length (the start of a path is recorded relative to
     //   the second pass' first summary row);
     //   17..99 columns: the form with ONE start field (fxg_clip_row_k).
@@ -125,12 +128,7 @@ static inline int fxg_make_plan(const fxg_batch *in, const fxg_params *p, const 
     pl->ck_per_wg = 0;
     ka.clip_ck = nullptr;
     if (pl->clip && (ka.clip_stride <= 255u || two_pass_k || !kform) && !getenv("FXG_NO_PACKED_CLIP")) {
-        // 36: the 33/34-base TruSeq adapters; 56 and 80 (round 5): 49..56 columns no longer pay for 64 (17.4 -> 27.7 ms between 48 and 49 bases,
-        // profiles/r04/p_clip_waves_by_adapter_len.txt) and 65..80 no longer for 100
-        // 44, 52, 60, 72, 88 (round 6): a bucket every 4 columns to 64 and every 8 to 88, so that no adapter pays for more than 8 % .. 12 % of padding columns
-        static const int pk[] = {4, 8, 9, 10, 11, 12, 13, 14, 15, 16, 20, 24, 28, 32, 36, 40, 44, 48, 52, 56, 60, 64, 72, 80, 88, 100};
-        int b = 100;
-        for (unsigned i = 0; i < sizeof pk / sizeof pk[0]; ++i) if (ka.alen <= pk[i]) { b = pk[i]; break; }
+        const int b = fxg_clip_bucket(ka.alen);      // the smallest instance that holds the adapter
         pl->amax = -b;
         if (two_pass_k) pl->ck_per_wg = (u64)FXG_CK_SLOTS * (u64)b * FXG_TBLOCK;
         // the pair table of the instance (fxg_kernels.h: fxg_clip_ptab_build): as many columns as the bucket, rounded up to whole 16-byte blocks

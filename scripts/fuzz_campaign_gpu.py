@@ -10,14 +10,14 @@ import numpy as np
 import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests")); sys.path.insert(0, ROOT)
-from helpers import assert_same, oracle_params, random_batch
+from helpers import assert_same, clip_long_bucket_ends, oracle_params, random_batch
 from oracle import fxoracle_py as fo
 from fastx_toolkit_amd import Engine, make_params
 
 rng = np.random.default_rng(int(sys.argv[1]))
 adapters = [b"AGATCGGAAGAGC", b"CCTTAAGG", b"ACGT", b"TGGAATTCTCGGGTGCCAAGGAACTCCAGTCAC", b"AGATCGGAAGAGCACACGTCTGAACTCCAGTCACNNNNNNATCTCGTATGCCGTCTTCTGCTTG", b"ANNTCGNA", b"GATTACAGATTACAGA", b"A" * 17]
 _r = np.random.default_rng(56)
-for _n in (17, 20, 21, 24, 33, 36, 37, 41, 44, 45, 49, 52, 53, 56, 57, 60, 61, 64, 65, 72, 73, 80, 81, 88, 89, 99):
+for _n in [x for x in clip_long_bucket_ends() if x not in (25, 28, 29, 32, 40, 48)]:     # both ends of the buckets beyond 16 columns (but for six lengths the campaign never had: its seeds keep their adapters)
     _a = bytes(_r.choice(list(b"ACGT"), size=_n).astype(np.uint8))
     adapters += [_a, _a[:_n // 3] + b"N" + _a[_n // 3 + 1:]]
 adapters += [b"agatcggaagagc", b"AGRYCGGAWGAGC", b"AGATCGGAAGAGCacacgtctgaactcc", b"ACGTRY" * 7, b"ACGTRYKMSWBDHVXZACGTACGT", b"NACGTNNACGTN", b"ANNNNNNNNNNNNNNT"]

@@ -138,108 +138,44 @@ static int emu_run(const FxgPlan &pl, uint64_t *counters, char *err, size_t cap)
     return FXG_OK;
 }
 
-// The clipper's instances, in groups that tests/emu_py.py compiles side by side (-DFXG_EMU_TU=k: group k alone, 0: everything else; no define:
-// the whole emulator in one unit).  A group answers EMU_NOT_MINE for a plan it holds no instance of.
-enum { EMU_NOT_MINE = -12345, FXG_EMU_CLIP_GROUPS = 7 };
-typedef int emu_clip_group_fn(const FxgPlan &, uint64_t *, char *, size_t);
+// The clipper's instances, in the units of fxg_clip_instances.h, which tests/emu_py.py compiles side by side (-DFXG_EMU_TU=k: unit k alone, 0: everything
+// else; no define: the whole emulator in one unit).  A unit answers EMU_NOT_MINE for a plan it holds no instance of.
+enum { EMU_NOT_MINE = -12345 };
+typedef int emu_clip_unit_fn(const FxgPlan &, uint64_t *, char *, size_t);
 #define EMU_HIDDEN __attribute__((visibility("hidden")))
-EMU_HIDDEN emu_clip_group_fn emu_clip_rest;         // the general instance (any adapter length)
-EMU_HIDDEN emu_clip_group_fn emu_clip_group1;
-EMU_HIDDEN emu_clip_group_fn emu_clip_group2;
-EMU_HIDDEN emu_clip_group_fn emu_clip_group3;
-EMU_HIDDEN emu_clip_group_fn emu_clip_group4;
-EMU_HIDDEN emu_clip_group_fn emu_clip_group5;
-EMU_HIDDEN emu_clip_group_fn emu_clip_group6;
-EMU_HIDDEN emu_clip_group_fn emu_clip_group7;
+#define EMU_CLIP_UNIT_FN_(K) emu_clip_unit##K
+#define EMU_CLIP_UNIT_FN(K) EMU_CLIP_UNIT_FN_(K)
+#define EMU_CLIP_DECLARE_UNIT(K) EMU_HIDDEN emu_clip_unit_fn EMU_CLIP_UNIT_FN(K);
+FXG_CLIP_FOR_UNITS(EMU_CLIP_DECLARE_UNIT)
+EMU_HIDDEN emu_clip_unit_fn emu_clip_rest;         // the general instance (any adapter length)
+
+#define EMU_CLIP_CASE_PACKED(N) case -N: return emu_run<-N, false>(pl, ctr, err, cap);
+#define EMU_CLIP_CASE_GENERAL(N) case N: return emu_run<N, false>(pl, ctr, err, cap);
+#define EMU_CLIP_DEFINE_UNIT(K) \
+    int EMU_CLIP_UNIT_FN(K)(const FxgPlan &pl, uint64_t *ctr, char *err, size_t cap) { switch (pl.amax) { FXG_CLIP_UNIT(K)(EMU_CLIP_CASE_PACKED, EMU_CLIP_CASE_GENERAL) default: return EMU_NOT_MINE; } }
+#if !defined(FXG_EMU_TU)
+FXG_CLIP_FOR_UNITS(EMU_CLIP_DEFINE_UNIT)
+#elif FXG_EMU_TU != 0
+EMU_CLIP_DEFINE_UNIT(FXG_EMU_TU)
+#endif
 #if !defined(FXG_EMU_TU) || FXG_EMU_TU == 1
-int emu_clip_group1(const FxgPlan &pl, uint64_t *ctr, char *err, size_t cap)
-{
-    switch (pl.amax) {
-    case -4: return emu_run<-4, false>(pl, ctr, err, cap);
-    case -8: return emu_run<-8, false>(pl, ctr, err, cap);
-    case -9: return emu_run<-9, false>(pl, ctr, err, cap);
-    case -10: return emu_run<-10, false>(pl, ctr, err, cap);
-    case -11: return emu_run<-11, false>(pl, ctr, err, cap);
-    case -12: return emu_run<-12, false>(pl, ctr, err, cap);
-    case -13: return emu_run<-13, false>(pl, ctr, err, cap);
-    case -14: return emu_run<-14, false>(pl, ctr, err, cap);
-    case -15: return emu_run<-15, false>(pl, ctr, err, cap);
-    case -16: return emu_run<-16, false>(pl, ctr, err, cap);
-    case 16: return emu_run<16, false>(pl, ctr, err, cap);
-    case 32: return emu_run<32, false>(pl, ctr, err, cap);
-    case 64: return emu_run<64, false>(pl, ctr, err, cap);
-    default: return EMU_NOT_MINE;
-    }
-}
 int emu_clip_rest(const FxgPlan &pl, uint64_t *ctr, char *err, size_t cap) { return emu_run<100, false>(pl, ctr, err, cap); }
-#endif
-#if !defined(FXG_EMU_TU) || FXG_EMU_TU == 2
-int emu_clip_group2(const FxgPlan &pl, uint64_t *ctr, char *err, size_t cap)
-{
-    switch (pl.amax) {
-    case -20: return emu_run<-20, false>(pl, ctr, err, cap);
-    case -24: return emu_run<-24, false>(pl, ctr, err, cap);
-    case -28: return emu_run<-28, false>(pl, ctr, err, cap);
-    case -32: return emu_run<-32, false>(pl, ctr, err, cap);
-    case -36: return emu_run<-36, false>(pl, ctr, err, cap);
-    case -40: return emu_run<-40, false>(pl, ctr, err, cap);
-    default: return EMU_NOT_MINE;
-    }
-}
-#endif
-#if !defined(FXG_EMU_TU) || FXG_EMU_TU == 3
-int emu_clip_group3(const FxgPlan &pl, uint64_t *ctr, char *err, size_t cap)
-{
-    switch (pl.amax) {
-    case -48: return emu_run<-48, false>(pl, ctr, err, cap);
-    case -56: return emu_run<-56, false>(pl, ctr, err, cap);
-    case -64: return emu_run<-64, false>(pl, ctr, err, cap);
-    default: return EMU_NOT_MINE;
-    }
-}
-#endif
-#if !defined(FXG_EMU_TU) || FXG_EMU_TU == 4
-int emu_clip_group4(const FxgPlan &pl, uint64_t *ctr, char *err, size_t cap)
-{
-    switch (pl.amax) {
-    case -80: return emu_run<-80, false>(pl, ctr, err, cap);
-    case -100: return emu_run<-100, false>(pl, ctr, err, cap);
-    default: return EMU_NOT_MINE;
-    }
-}
-#endif
-#if !defined(FXG_EMU_TU) || FXG_EMU_TU == 5
-int emu_clip_group5(const FxgPlan &pl, uint64_t *ctr, char *err, size_t cap)
-{
-    switch (pl.amax) {
-    case -44: return emu_run<-44, false>(pl, ctr, err, cap);       // (the buckets of round 6, where the N instances used to be: an N is a column pattern of the pair table now)
-    case -52: return emu_run<-52, false>(pl, ctr, err, cap);
-    default: return EMU_NOT_MINE;
-    }
-}
-#endif
-#if !defined(FXG_EMU_TU) || FXG_EMU_TU == 6
-int emu_clip_group6(const FxgPlan &pl, uint64_t *ctr, char *err, size_t cap)
-{
-    switch (pl.amax) {
-    case -60: return emu_run<-60, false>(pl, ctr, err, cap);
-    case -72: return emu_run<-72, false>(pl, ctr, err, cap);
-    default: return EMU_NOT_MINE;
-    }
-}
-#endif
-#if !defined(FXG_EMU_TU) || FXG_EMU_TU == 7
-int emu_clip_group7(const FxgPlan &pl, uint64_t *ctr, char *err, size_t cap)
-{
-    switch (pl.amax) {
-    case -88: return emu_run<-88, false>(pl, ctr, err, cap);
-    default: return EMU_NOT_MINE;
-    }
-}
 #endif
 
 #if !defined(FXG_EMU_TU) || FXG_EMU_TU == 0
-static emu_clip_group_fn *const emu_clip_groups[FXG_EMU_CLIP_GROUPS] = {emu_clip_group1, emu_clip_group2, emu_clip_group3, emu_clip_group4, emu_clip_group5, emu_clip_group6, emu_clip_group7};
+#define EMU_CLIP_UNIT_ENTRY(K) EMU_CLIP_UNIT_FN(K),
+static emu_clip_unit_fn *const emu_clip_units[FXG_CLIP_UNITS] = {FXG_CLIP_FOR_UNITS(EMU_CLIP_UNIT_ENTRY)};
+// the table itself, for the test that holds it against the tests' own list (tests/test_clip_instances.py): every packed bucket with the unit that holds its
+// instance, in the table's order; returns how many there are (more than `cap`: only the first `cap` were written)
+extern "C" int fxg_emu_clip_buckets(int *bucket, int *unit, int cap)
+{
+    int n = 0;
+#define EMU_CLIP_EXPORT_UNIT(K) { const int held[] = {FXG_CLIP_UNIT_PACKED(K)}; for (int b : held) { if (n < cap) { bucket[n] = b; unit[n] = K; } ++n; } }
+    FXG_CLIP_FOR_UNITS(EMU_CLIP_EXPORT_UNIT)
+#undef EMU_CLIP_EXPORT_UNIT
+    return n;
+}
+extern "C" int fxg_emu_clip_units(void) { return FXG_CLIP_UNITS; }
 
 // clip history (fxg_history.h): the same per-column bodies the pre-pass kernels run, serially
 struct fxg_emu_hist {
@@ -314,8 +250,8 @@ extern "C" int fxg_emu_run_pipeline_hist(const fxg_batch *in, const fxg_params *
     uint64_t *ctr = out->counters;
     if (pl.group_a) {
         if (pl.amax == 0) return emu_run<0, false>(pl, ctr, err, cap);
-        for (int g = 0; g < FXG_EMU_CLIP_GROUPS; ++g) {
-            const int r = emu_clip_groups[g](pl, ctr, err, cap);
+        for (int g = 0; g < FXG_CLIP_UNITS; ++g) {
+            const int r = emu_clip_units[g](pl, ctr, err, cap);
             if (r != EMU_NOT_MINE) return r;
         }
         return emu_clip_rest(pl, ctr, err, cap);

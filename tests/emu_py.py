@@ -24,8 +24,8 @@ class Out(C.Structure):
 _CXX = ["hipcc", "--cuda-host-only", "-O2", "-std=c++17", "-ffp-contract=off", "-fPIC", "-Wno-pass-failed", "-DFXG_HOST_EMULATION"]
 _LINK = ["hipcc", "-shared", "-fPIC"]         # (objects only: with --cuda-host-only the driver would read them as sources)
 _CSRC = os.path.join(_HERE, "..", "fastx_toolkit_amd", "csrc")
-_EMU_DEPS = [os.path.join(_CSRC, f) for f in ("fxg_device.h", "fxg_kernels.h", "fxg_plan.h", "fxg_text.h", "fxg_rows.h", "fxg_history.h", "fxg_stats.h")]
-EMU_UNITS = 8               # fxg_emu.cpp: -DFXG_EMU_TU=0 (everything but the clipper's instances) and its seven groups of clip instances
+_EMU_DEPS = [os.path.join(_CSRC, f) for f in ("fxg_device.h", "fxg_clip_instances.h", "fxg_kernels.h", "fxg_plan.h", "fxg_text.h", "fxg_rows.h", "fxg_history.h", "fxg_stats.h")]
+EMU_UNITS = 8               # fxg_emu.cpp: -DFXG_EMU_TU=0 (everything but the clipper's instances) and one per unit of clip instances (csrc/fxg_clip_instances.h; tests/test_clip_instances.py)
 
 
 def _emu_objects(defs):
@@ -275,3 +275,11 @@ def fasta_weights(ix, n, res, guard=None):
     if rc != 0:
         raise ValueError("emu fasta_weights rc=%d" % rc)
     return list(w)
+
+
+def clip_table():
+    """([(bucket, unit), ...] in the order of csrc/fxg_clip_instances.h, number of units): the engine's table of packed clip instances as the emulator was compiled with it."""
+    n = lib().fxg_emu_clip_buckets(None, None, 0)
+    b, u = (C.c_int * n)(), (C.c_int * n)()
+    assert lib().fxg_emu_clip_buckets(b, u, n) == n
+    return list(zip(b, u)), lib().fxg_emu_clip_units()

@@ -167,6 +167,40 @@ FLAG_ERROR_CASES = [
 ]
 
 
+# The packed clip instances the engine must offer, fxg_kernel_tiles<-B,0> for each B: the tests' OWN statement of the set (never read out of the code under
+# test; test_clip_instances.py holds csrc/fxg_clip_instances.h against it).  Every other list of buckets, instances or bucket ends is derived from it.
+CLIP_BUCKETS = [4, 8, 9, 10, 11, 12, 13, 14, 15, 16, 20, 24, 28, 32, 36, 40, 44, 48, 52, 56, 60, 64, 72, 80, 88, 100]
+CLIP_MAX_ADAPTER = 99          # include/fxg.h FXG_MAX_ADAPTER
+
+
+def clip_bucket(alen):
+    """The bucket of an adapter of `alen` bases: the smallest one that holds it."""
+    return min(b for b in CLIP_BUCKETS if b >= alen)
+
+
+def clip_packed_instance(adapter):
+    """"<-B,0>" of the packed instance the plan picks for `adapter` (bytes), None where it picks the general form (more than 16 columns and more than six
+    distinct bytes besides N: csrc/fxg_plan.h)."""
+    if len(adapter) > 16 and len(set(adapter) - {ord("N")}) > 6:
+        return None
+    return "<-%d,0>" % clip_bucket(len(adapter))
+
+
+def clip_instance_names(long_adapters):
+    """The kernel names of the packed instances of more than 16 columns (the one-start-field forms), or of those of up to 16 (the register forms)."""
+    return {"fxg_kernel_tiles<-%d,0>" % b for b in CLIP_BUCKETS if (b > 16) == bool(long_adapters)}
+
+
+def clip_long_bucket_ends():
+    """Both ends of every bucket of more than 16 columns, in bucket order: the shortest and the longest adapter (of at most CLIP_MAX_ADAPTER bases) it serves."""
+    ends, below = [], 16
+    for b in CLIP_BUCKETS:
+        if b > 16:
+            ends += [below + 1, min(b, CLIP_MAX_ADAPTER)]
+        below = b
+    return ends
+
+
 def adversarial_clip_cases(long_adapters):
     """Yields (name, bases, qual, params_dict): inputs built to stress the clip kernels' bound on the best path's length -- every adapter
     length 1..16 (all packed buckets of the two-pass form) or, with long_adapters, 17..99 (every bucket of the one-pass in-place form);
@@ -174,10 +208,11 @@ def adversarial_clip_cases(long_adapters):
     than the adapter, best cells in the first / last rows, an insertion / deletion right before a planted adapter."""
     rng = np.random.default_rng(11)
     acgt = np.frombuffer(b"ACGT", dtype=np.uint8)
+    long_ends = clip_long_bucket_ends()
     for trial in range(128 if long_adapters else 96):
         alen = 1 + trial % 16
-        if long_adapters:                                                       # both ends of every bucket (44, 52, 60, 72, 88: round 6)
-            alen = [17, 20, 21, 24, 25, 28, 29, 32, 33, 36, 37, 40, 41, 44, 45, 48, 49, 52, 53, 56, 57, 60, 61, 64, 65, 72, 73, 80, 81, 88, 89, 99][trial % 32]
+        if long_adapters:                                                       # both ends of every bucket (32 lengths: trial % 32 decides which one meets which kind)
+            alen = long_ends[trial % 32]
         kind = trial % 6
         if kind == 0:
             ad = bytes(rng.choice(acgt, size=alen))

@@ -27,8 +27,9 @@ import pytest
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
+sys.path[:0] = [ROOT, HERE]         # (the children run this file as a script)
+from helpers import CLIP_BUCKETS  # noqa: E402
 FULL = b"AGATCGGAAGAGCACACGTCTGAACTCCAGTCACATCACGATCTCGTATGCCGTCTTCTGCTTGAAAAAAAAAAGGGGGGGGGGCCCCCCCCCCTTTTTTTTT"
-BUCKETS = [4, 8, 9, 10, 11, 12, 13, 14, 15, 16, 20, 24, 28, 32, 36, 40, 44, 48, 52, 56, 60, 64, 72, 80, 88, 100]    # fxg_plan.h pk[]
 CHILD_TIMEOUT = 120
 
 
@@ -71,7 +72,7 @@ def _cases():
             add("census.s%d.st%d.k%d.ragged" % (stride, pd["stages"], pd.get("nf_keep_n", 0)), stride=stride, n=131, lens="short", params=pd,
                 guard="before" if stride % 2 else "after")
     # ---- the clipper: every bucket, staged and over the batch, the last read ending in adapter prefixes and all adapter ----
-    for A in BUCKETS:
+    for A in CLIP_BUCKETS:
         A = min(A, 99)
         ad = FULL[:A].decode()
         strides = (200, 180, 101) if A <= 16 else (256, 252, 150)

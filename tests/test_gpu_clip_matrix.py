@@ -33,7 +33,7 @@ WORKER = r"""
 import json, os, sys
 sys.path.insert(0, sys.argv[1]); sys.path.insert(0, os.path.join(sys.argv[1], "tests"))
 import numpy as np, torch
-from helpers import adversarial_clip_cases, oracle_params, assert_same, random_batch
+from helpers import adversarial_clip_cases, oracle_params, assert_same, random_batch, clip_packed_instance
 from oracle import fxoracle_py as fo
 from fastx_toolkit_amd import Engine, make_params
 eng = Engine(0)
@@ -53,11 +53,7 @@ def run(b, q, lens, pd):
     return once(b, q, lens, pd)
 rejected = json.loads(sys.argv[2])                    # instances the ISA check refused in this library: NEVER launched (round 6: a refused 64-column instance at
 kernels, n, refused = set(), 0, {}                    # four waves faulted the GPU -- code that runs with EXEC = 0 ahead of its restore can compute any address)
-BUCKETS = [4, 8, 9, 10, 11, 12, 13, 14, 15, 16, 20, 24, 28, 32, 36, 40, 44, 48, 52, 56, 60, 64, 72, 80, 88, 100]     # fxg_plan.h
-def inst_of(ad):
-    if len(ad) > 16 and len(set(ad) - {ord("N")}) > 6:
-        return None                                   # the general form
-    return "<-%d,0>" % [b for b in BUCKETS if len(ad) <= b][0]
+inst_of = clip_packed_instance                        # None: the general form
 WAVES = int(sys.argv[3])
 def shipped_waves(inst):                              # fxg_clip_waves (csrc/fxg_kernels.h): the budget the product builds the instance for
     cols = -int(inst[1:inst.index(",")])
