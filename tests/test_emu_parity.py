@@ -146,7 +146,8 @@ def test_emulated_clip_over_the_batch_and_over_the_staged_tile(monkeypatch, mode
 def test_clip_global_window_clamp_on_huge_batches():
     """The over-the-batch clip form clamps its two-dword window to the array's last dword.  The number of dwords behind a row is a 64-bit count:
     a batch of 8 GiB and more (30 M reads at a 300-byte stride) used to wrap it into a negative int for its early rows, and every window load
-    then went to a negative index.  The helper the kernels call, on totals no test could allocate."""
+    then went to a negative index.  The helper the kernels call, on totals the CPU tier cannot allocate; the kernel itself runs at such a total on the
+    GPU (tests/test_gpu_large_offsets.py::test_large_offsets_family[clip13gl-*]: FXG_CLIP_GLOBAL=1 on 137 M reads x 100 bytes, 12.8 GiB per array)."""
     import ctypes as C
     f = emu.lib().fxg_emu_gl_last_dword
     f.argtypes = [C.c_uint64, C.c_uint64]
