@@ -59,10 +59,11 @@ FXG_HD FxgBcWin fxg_bc_window(const uint8_t *text, u32 s, u32 e, u32 BL, u32 eol
     if (F == 0u) return w;
     const u32 ws = eol ? e - F : s;
     const u32 a = ws & ~3u;
+    const u32 span = ws + F - a;                                 // bytes from the first dword's start to the window's end: 1 .. F + 3
 #pragma unroll
     for (u32 k = 0; k < (FXG_MAX_BARCODE + 4u) / 4u; ++k) {      // (unrolled: no lane-divergent loop with live-out values)
         const u32 q = a + 4u * k;
-        if (q < ws + F) {
+        if (4u * k < span) {                                     // (not q < ws + F: in the last 64 bytes below 2^32 q wraps and would admit a load of the block's first dword)
             u32 d;
             __builtin_memcpy(&d, text + q, 4);
 #pragma unroll

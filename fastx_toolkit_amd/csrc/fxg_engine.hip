@@ -596,7 +596,7 @@ extern "C" int fxg_fastq_format(fxg_ctx *c, const uint8_t *d_text, int lines_per
     else hipLaunchKernelGGL(fxg_kernel_text_format<2>, dim3(fgrid), dim3(FXG_BLOCK), 0, c->stream, a);
     FXG_HIP(c, hipGetLastError());
     FXG_HIP(c, hipStreamSynchronize(c->stream));
-    *out_bytes = ((last_scan + last_item) & ((1ull << 40) - 1ull));
+    *out_bytes = ((last_scan + last_item) & FXG_FMT_OFF_MASK);
     return FXG_OK;
 }
 

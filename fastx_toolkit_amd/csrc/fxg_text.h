@@ -434,7 +434,22 @@ struct FxgFormatArgs {
 
 FXG_HD u32 fxg_num_width(int v) { return (v < 0 ? 1u : 0u) + ((v <= -10 || v >= 10) ? 2u : 1u); }     // -15..93
 
-// item r = output bytes of record r in the low 40 bits, keep flag above (the scan then yields offset and rank)
+// item r = output bytes of record r in the low 40 bits, keep flag above (the scan then yields the offset and, modulo 2^24, the rank)
+#define FXG_FMT_OFF_BITS 40
+#define FXG_FMT_OFF_MASK ((1ull << FXG_FMT_OFF_BITS) - 1ull)
+#define FXG_FMT_RANK_MASK ((1ull << (64 - FXG_FMT_OFF_BITS)) - 1ull)
+
+// The kept records before record r, from the scanned items.  The scan carries the rank modulo 2^24 only, and a block at the limit
+// (text_len = 0xFFFFFFF0) holds up to 2^30 records: taken as it stands, the rank of the 2^24-th kept record and of those after it named the
+// packed bases of record rank - 2^24.  Between two records 2^23 apart the rank grows by at most 2^23, so the steps from record 0 to r over
+// every 2^23-th record are each exact modulo 2^24.  Blocks of up to 2^23 records (the tools' are far smaller) take no step but the last.
+FXG_HD u64 fxg_text_rank(const u64 *item_scan, u64 r)
+{
+    u64 rank = 0;
+    for (u64 i = 1ull << 23; i < r; i += 1ull << 23) rank += ((item_scan[i] >> FXG_FMT_OFF_BITS) - rank) & FXG_FMT_RANK_MASK;
+    return rank + (((item_scan[r] >> FXG_FMT_OFF_BITS) - rank) & FXG_FMT_RANK_MASK);
+}
+
 template <int LPR>
 FXG_HD u64 fxg_text_size_record(const FxgFormatArgs &a, u64 r)
 {
@@ -458,7 +473,7 @@ FXG_HD u64 fxg_text_size_record(const FxgFormatArgs &a, u64 r)
             }
             bytes += (u64)name2_len + qbytes + 3u;                                  // '+', name2, LF, qualities, LF
         }
-        v = bytes | (1ull << 40);
+        v = bytes | (1ull << FXG_FMT_OFF_BITS);
     }
     return v;
 }
@@ -486,14 +501,14 @@ FXG_HD void fxg_text_format_record(const FxgFormatArgs &a, u64 r, u32 l)
     const u32 w = a.res[r];
     if (!((w >> 16) & 1u)) return;
     const u64 sc = a.item_scan[r];
-    const u64 off = sc & ((1ull << 40) - 1ull), rank = sc >> 40;
+    const u64 off = sc & FXG_FMT_OFF_MASK;
     const u64 b = (u64)LPR * r;
     const u32 o0 = a.ls[b], o1 = a.ls[b + 1];
     const u32 name_len = a.le[b] - o0 - 1u;
     const u32 len = w & 0xFFFFu;
     const bool fastq = (LPR == 4 && !a.out_fasta);
     uint8_t *d = a.out + off;
-    const u64 po = a.pk_bases ? a.pk_off[rank] : 0ull;
+    const u64 po = a.pk_bases ? a.pk_off[fxg_text_rank(a.item_scan, r)] : 0ull;
     if (l == 0) { d[0] = fastq ? '@' : '>'; d[1 + name_len] = '\n'; d[2 + name_len + len] = '\n'; }
     fxg_copy_bytes(d + 1, a.text + o0 + 1, name_len, l, 16, 0);
     if (a.pk_bases) fxg_copy_bytes(d + 2 + name_len, a.pk_bases + po, len, l, 16, 0);

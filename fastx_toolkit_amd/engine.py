@@ -160,18 +160,31 @@ def load_library(path=None):
 
 
 class TextIndex:
-    """Device line index of a block of text (fxg_fastq_index): line starts, line ends after chomp, per-record flags."""
+    """Device line index of a block of text (fxg_fastq_index): line starts, line ends after chomp, per-record flags.  The engine's line
+    array holds u32 byte offsets (a block may be 0xFFFFFFF0 bytes long); `line` is the int32 allocation the ABI is given, starts / ends are
+    uint32 views of it, so their values are 0 .. 2^32 - 1 wherever they are read (.item(), .cpu().numpy(), .to(torch.int64))."""
 
     def __init__(self, line, cap_lines, flags, lpr):
         self.line, self.cap_lines, self.flags, self.lpr = line, cap_lines, flags, lpr
 
+    def _u32(self, t):
+        import torch
+        return t if t.dtype == torch.uint32 else t.view(torch.uint32)
+
     @property
     def starts(self):
-        return self.line[:self.cap_lines]
+        return self._u32(self.line[:self.cap_lines])
 
     @property
     def ends(self):
-        return self.line[self.cap_lines:]
+        return self._u32(self.line[self.cap_lines:])
+
+    def record_bytes(self, n):
+        """Bytes of records 0 .. n of the block: the start of line lpr * n minus the start of line 0, both taken as unsigned."""
+        if not n:
+            return 0
+        s = self.starts
+        return (int(s[self.lpr * n].item()) & 0xFFFFFFFF) - (int(s[0].item()) & 0xFFFFFFFF)
 
 
 class FxgError(RuntimeError):
@@ -470,10 +483,13 @@ class Engine:
         """Partition the n records of an indexed block (fastq_index) by the table of barcode_prepare.  Returns (out, bin_bytes, bin_records,
         rec_bin): out holds bin 0's records, then bin 1's, ... (a view of exactly their bytes); rec_bin (int16 tensor) or None."""
         bins = self._bc_bins
-        starts = ix.starts
-        nbytes = int(starts[ix.lpr * n].item()) - int(starts[0].item()) if n else 0
+        nbytes = ix.record_bytes(n)
+        if nbytes < 0 or nbytes > text_len:
+            raise FxgError("barcode_split: records 0..%d span %d bytes of a block of %d" % (n, nbytes, text_len))
         if out is None:
             out = self.torch.empty(max(nbytes, 1), dtype=self.torch.uint8, device=self.device)
+        elif out.numel() < nbytes:
+            raise FxgError("barcode_split: out holds %d bytes, the records need %d" % (out.numel(), nbytes))
         rb = self.torch.empty(max(n, 1), dtype=self.torch.int16, device=self.device) if rec_bin else None
         bb, br = (C.c_uint64 * bins)(), (C.c_uint64 * bins)()
         self._after_torch()

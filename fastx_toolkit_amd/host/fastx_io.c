@@ -49,6 +49,18 @@ size_t fxh_tune_pipe(int fd)
     return have > 0 ? (size_t)have : 65536u;
 }
 
+/* FXH_READ_BUFFER_MB as bytes: 0 when unset or not positive (the caller's default then); at most FXH_READ_BUFFER_MB_MAX, because one block
+ * is one engine call and the C-ABI takes blocks of up to 0xFFFFFFF0 bytes (include/fxg.h: its line index holds 32-bit offsets). */
+size_t fxh_read_buffer_bytes(void)
+{
+    const char *e = getenv("FXH_READ_BUFFER_MB");
+    if (!e) return 0;
+    long v = strtol(e, NULL, 10);
+    if (v <= 0) return 0;
+    if (v > FXH_READ_BUFFER_MB_MAX) v = FXH_READ_BUFFER_MB_MAX;
+    return (size_t)v << 20;
+}
+
 struct fxh_reader *fxh_reader_open(const char *filename, size_t capacity)
 {
     struct fxh_reader *r = (struct fxh_reader *)calloc(1, sizeof *r);
@@ -602,8 +614,7 @@ void fastx_init_reader(FASTX *fx, const char *filename, ALLOWED_INPUT_FILE_TYPES
 {
     if (fx == NULL) errx(1, "Internal error: pFASTX==NULL (%s:%d)", __FILE__, __LINE__);
     memset(fx, 0, sizeof *fx);
-    const char *cap_env = getenv("FXH_READ_BUFFER_MB");
-    fx->reader = fxh_reader_open(filename, cap_env && atoi(cap_env) > 0 ? (size_t)atoi(cap_env) << 20 : 0);
+    fx->reader = fxh_reader_open(filename, fxh_read_buffer_bytes());
     strncpy(fx->input_file_name, filename, sizeof fx->input_file_name - 1);
     fx->allow_input_filetype = allowed_input_filetype;
     fx->allow_lowercase = allow_lowercase;

@@ -39,6 +39,8 @@ struct fxh_rawrec {
     char errmsg[768];
 };
 
+#define FXH_READ_BUFFER_MB_MAX 4095L     /* 0xFFF00000 bytes: the largest whole number of MB below the C-ABI's block limit (0xFFFFFFF0) */
+size_t fxh_read_buffer_bytes(void);     /* FXH_READ_BUFFER_MB in bytes, clamped to FXH_READ_BUFFER_MB_MAX; 0 = not set */
 struct fxh_reader *fxh_reader_open(const char *filename, size_t capacity);
 struct fxh_reader *fxh_reader_open_range(const char *filename, size_t capacity, off_t start, off_t limit);   /* regular file, bytes [start, limit) */
 struct fxh_writer *fxh_writer_open_file(const char *filename, int gzip);

@@ -122,7 +122,6 @@ int fxh_run_parts(FASTX *fx, const fxg_params *p, fxh_totals *tot, int k)
     (void)prctl(PR_SET_PDEATHSIG, SIGTERM);      /* the child: a tool process that was killed takes its sharded attempt along */
     fxh_part *pt = (fxh_part *)calloc((size_t)k, sizeof(fxh_part));
     if (!pt) err(1, "out of memory");
-    const char *cap_env = getenv("FXH_READ_BUFFER_MB");
     for (int r = 0; r < k; ++r) {
         pt[r].p = p; pt[r].part = r; pt[r].nparts = k; pt[r].start = cut[r]; pt[r].limit = cut[r + 1];
         fxh_part_name(fx, r, pt[r].name, sizeof pt[r].name);
@@ -130,7 +129,7 @@ int fxh_run_parts(FASTX *fx, const fxg_params *p, fxh_totals *tot, int k)
         FASTX *f = (FASTX *)malloc(sizeof(FASTX));
         if (!f) err(1, "out of memory");
         memcpy(f, fx, sizeof(FASTX));
-        f->reader = fxh_reader_open_range(fx->input_file_name, cap_env && atoi(cap_env) > 0 ? (size_t)atoi(cap_env) << 20 : 0, cut[r], cut[r + 1]);
+        f->reader = fxh_reader_open_range(fx->input_file_name, fxh_read_buffer_bytes(), cut[r], cut[r + 1]);
         f->writer = fxh_writer_open_fd(part_fd[r]);
         f->input_line_number = 0; f->num_input_sequences = f->num_input_reads = f->num_output_sequences = f->num_output_reads = 0;
         pt[r].fx = f;

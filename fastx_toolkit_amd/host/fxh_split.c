@@ -375,8 +375,7 @@ int fxh_split_run(const fxh_split_opts *o)
     {
         struct stat sb;
         if (fstat(STDIN_FILENO, &sb) == 0 && S_ISFIFO(sb.st_mode)) cap = (size_t)16 << 20;
-        const char *e = getenv("FXH_READ_BUFFER_MB");
-        if (e && atoi(e) > 0) cap = (size_t)atoi(e) << 20;
+        if (fxh_read_buffer_bytes()) cap = fxh_read_buffer_bytes();
     }
     struct fxh_reader *rd = fxh_reader_open("-", cap);
     fxh_prefetch pf;
