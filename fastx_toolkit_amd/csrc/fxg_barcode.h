@@ -160,6 +160,40 @@ struct FxgBcArgs {
     u64 *totals;                      // [2 * bins], zeroed before classify: bytes per bin, then records per bin
 };
 
+// ---- host side of fxg_barcode_prepare / _split, one copy for the engine and tests/emu ----
+static inline int fxg_bc_set_check(const fxg_barcode_set *set, char *err, size_t cap)
+{
+    const u32 E = set->entries, BL = set->barcode_len;
+    if (set->bins < 1 || set->bins > FXG_MAX_BARCODE_BINS) FXG_PLAN_FAIL("barcode split: %u bins (1 .. %d)", set->bins, FXG_MAX_BARCODE_BINS);
+    if (BL > FXG_MAX_BARCODE || (E > 0 && BL == 0)) FXG_PLAN_FAIL("barcode length %u (1 .. %d)", BL, FXG_MAX_BARCODE);
+    if (E > 0 && (!set->bases || !set->len || !set->bin)) FXG_PLAN_FAIL("barcode table without bases / lengths / bins");
+    return FXG_OK;
+}
+static inline int fxg_bc_set_encode(const fxg_barcode_set *set, FxgBcEntry *tab, char *err, size_t cap)      // the entries of a checked set into tab[set->entries]
+{
+    for (u32 k = 0; k < set->entries; ++k) {
+        const u32 L = set->len[k];
+        if (L > set->barcode_len || set->bin[k] >= set->bins) FXG_PLAN_FAIL("barcode entry %u: length %u, bin %u", k, L, set->bin[k]);
+        if (!fxg_bc_encode_entry(set->bases + (size_t)k * FXG_MAX_BARCODE, L, set->barcode_len, set->bin[k], tab[k])) FXG_PLAN_FAIL("barcode entry %u: a base that is not A, C, G or T", k);
+    }
+    return FXG_OK;
+}
+// what a split needs (bins: of the prepared table, 0 = there is none), and the empty totals: the caller has nothing more to do for n == 0
+static inline int fxg_bc_split_check(u32 bins, const uint8_t *text, u64 text_len, int lpr, const u32 *line, u64 cap_lines, u64 n, const uint8_t *out, uint64_t *bin_bytes, uint64_t *bin_records,
+                                     char *err, size_t cap)
+{
+    if (!text || !line || !bin_bytes || !bin_records || !fxg_text_lpr_ok(lpr)) return FXG_E_INVALID;
+    if (!bins) FXG_PLAN_FAIL("fxg_barcode_split: no table (fxg_barcode_prepare)");
+    memset(bin_bytes, 0, bins * sizeof(uint64_t));
+    memset(bin_records, 0, bins * sizeof(uint64_t));
+    if (n == 0) return FXG_OK;
+    if (!out) return FXG_E_INVALID;
+    if (((uintptr_t)text & 3u) != 0) FXG_PLAN_FAIL("fxg_barcode_split: the text must be 4-byte aligned");
+    if (fxg_text_check_len(text_len, err, cap) != FXG_OK) return FXG_E_INVALID;
+    if ((u64)lpr * n + 1 > cap_lines) FXG_PLAN_FAIL("fxg_barcode_split: %llu records need more than %llu lines", (unsigned long long)n, (unsigned long long)cap_lines);
+    return FXG_OK;
+}
+
 #ifndef FXG_HOST_EMULATION
 // classify: one lane per record.  The table goes through LDS FXG_BC_STAGE entries at a time (every lane then reads the same entry: a
 // broadcast); a wave skips the rest of the table once every lane has found an entry with no mismatch, after which no later entry can win.

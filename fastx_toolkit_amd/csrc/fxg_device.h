@@ -5,6 +5,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <cstdio>
+#include <cstring>
 
 #include "../../include/fxg.h"
 
@@ -14,6 +16,11 @@ typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
 // pure per-thread helpers are __host__ __device__ so that tests/emu can run them on the CPU
 #define FXG_HD __host__ __device__ __forceinline__
+// a refused request, in the host-only checks the engine and tests/emu share (fxg_plan.h and the family headers): the message into the caller's buffer
+#define FXG_PLAN_FAIL(...) do { snprintf(err, cap, __VA_ARGS__); return FXG_E_INVALID; } while (0)
+// a block of text (fxg_text.h, fxg_barcode.h): its line starts are 32-bit, so it ends below 2^32 with room for the 16-byte loads at its end; FASTQ or FASTA
+static inline int fxg_text_check_len(unsigned long long text_len, char *err, size_t cap) { if (text_len > 0xFFFFFFF0ull) FXG_PLAN_FAIL("text block too large (%llu bytes)", text_len); return FXG_OK; }
+static inline bool fxg_text_lpr_ok(int lpr) { return lpr == 4 || lpr == 2; }
 
 // timing-ablation switches exist only in -DFXG_ABLATION builds (scripts/ablate.py); the product build folds them to 0
 #if defined(FXG_ABLATION) || defined(FXG_DBG_BITS)      // (FXG_DBG_BITS: the switches alone, without the phase clocks and their barrier -- the product's own timing with a phase taken out)

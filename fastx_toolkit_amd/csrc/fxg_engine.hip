@@ -18,9 +18,9 @@ extern "C" int fxg_ctx_create(int device_id, fxg_ctx **out)
     if (!c) return FXG_E_NOMEM;
     c->device = device_id;
     hipDeviceProp_t prop;
-    if (hipSetDevice(device_id) != hipSuccess || hipGetDeviceProperties(&prop, device_id) != hipSuccess) { free(c); return FXG_E_HIP; }
+    if (hipSetDevice(device_id) != hipSuccess || hipGetDeviceProperties(&prop, device_id) != hipSuccess ||
+        hipStreamCreateWithFlags(&c->own_stream, hipStreamNonBlocking) != hipSuccess) { fxg_ctx_destroy(c); return FXG_E_HIP; }
     c->cus = prop.multiProcessorCount;
-    if (hipStreamCreateWithFlags(&c->own_stream, hipStreamNonBlocking) != hipSuccess) { free(c); return FXG_E_HIP; }
     c->stream = c->own_stream;
     { const char *e = getenv("FXG_BLOCKS_PER_CU"); c->env_blocks_per_cu = (e && atoi(e) > 0 && atoi(e) <= 16) ? atoi(e) : 0; }
     { const char *e = getenv("FXG_WORKERS"); c->env_workers = (e && atoi(e) > 0) ? atoi(e) : 0; }
@@ -29,26 +29,25 @@ extern "C" int fxg_ctx_create(int device_id, fxg_ctx **out)
     { const char *e = getenv("FXG_TICKET_GROUPS"); c->env_ticket_groups = (e && atoi(e) > 0 && atoi(e) <= FXG_TICKET_GROUPS) ? atoi(e) : 0; }
     if (hipEventCreate(&c->ev0) != hipSuccess || hipEventCreate(&c->ev1) != hipSuccess ||
         hipMalloc((void **)&c->errflag, (FXG_CTRL_WORDS + FXG_TICKET_GROUPS * FXG_TICKET_STRIDE) * sizeof(u32)) != hipSuccess ||
-        hipMalloc((void **)&c->counters_scratch, FXG_NCOUNTERS * sizeof(u64)) != hipSuccess) {
-        free(c);
-        return FXG_E_HIP;
-    }
+        hipMalloc((void **)&c->counters_scratch, FXG_NCOUNTERS * sizeof(u64)) != hipSuccess) { fxg_ctx_destroy(c); return FXG_E_HIP; }
     *out = c;
     return FXG_OK;
 }
 
+// also the one way out of a fxg_ctx_create that failed half way: whatever exists by then is released, nothing else is touched
 extern "C" void fxg_ctx_destroy(fxg_ctx *c)
 {
     if (!c) return;
     (void)hipSetDevice(c->device);
-    (void)hipStreamSynchronize(c->stream);
+    if (c->stream) (void)hipStreamSynchronize(c->stream);
     (void)hipFree(c->status); (void)hipFree(c->errflag); (void)hipFree(c->counters_scratch);
     (void)hipFree(c->text_ws); (void)hipFree(c->text_state); (void)hipFree(c->fb_blk);
     (void)hipFree(c->hist_buf[0]); (void)hipFree(c->hist_buf[1]); (void)hipFree(c->hist_w); (void)hipFree(c->hist_ws); (void)hipFree(c->stats_ws); (void)hipFree(c->clip_ck);
     (void)hipFree(c->bc_tab); (void)hipFree(c->bc_ws);
-    (void)hipEventDestroy(c->ev0); (void)hipEventDestroy(c->ev1);
+    if (c->ev0) (void)hipEventDestroy(c->ev0);
+    if (c->ev1) (void)hipEventDestroy(c->ev1);
     for (int i = 0; i < FXG_KEV_RING; ++i) { if (c->kev0[i]) (void)hipEventDestroy(c->kev0[i]); if (c->kev1[i]) (void)hipEventDestroy(c->kev1[i]); }
-    (void)hipStreamDestroy(c->own_stream);
+    if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
     free(c);
 }
 
@@ -131,9 +130,8 @@ extern "C" int fxg_timer_stop(fxg_ctx *c, float *ms)
 
 int fxg_enqueue_finish_counters(fxg_ctx *c, const FxgKArgs &ka, u64 *counters)
 {
-    hipLaunchKernelGGL(fxg_kernel_finish_counters, dim3(1), dim3(64), 0, c->stream, (const u64 *)ka.tally, ka.stages, (const u32 *)c->errflag,
-                       (const u64 *)(c->errflag + 2), counters ? counters : c->counters_scratch);
-    FXG_HIP(c, hipGetLastError());
+    FXG_LAUNCH(c, fxg_kernel_finish_counters, 1, 64, 0, (const u64 *)ka.tally, ka.stages, (const u32 *)c->errflag, (const u64 *)(c->errflag + 2),
+               counters ? counters : c->counters_scratch);
     return FXG_OK;
 }
 
@@ -159,47 +157,26 @@ extern "C" int fxg_set_clip_history(fxg_ctx *c, int on)
     return FXG_OK;
 }
 
-// Builds the extended queries of one batch and moves the buffer on.  Returns FXG_OK with *use = 0 when the batch cannot see a
-// stale tail (fixed length, nothing longer before it): the clip kernel then reads the batch itself.
-static int fxg_hist_prepass(fxg_ctx *c, const fxg_batch *in, u32 T, u32 estride, FxgKArgs *ka, int *use)
+// Builds the extended queries of one batch, points the plan's clip stage at them and moves the buffer on.  A batch that cannot see a stale tail
+// (fxg_hist_shortcut) only moves the buffer on: the clip kernel then reads the batch itself.
+static int fxg_hist_prepass(fxg_ctx *c, const fxg_batch *in, u32 estride, FxgPlan &pl)
 {
-    const u32 lmax = in->len ? in->stride : in->fixed_len;
     const int cur = c->hist_cur;
-    *use = 0;
-    if (!in->len && c->hist_wcap <= in->fixed_len) {
-        hipLaunchKernelGGL(fxg_kernel_hist_fixed, dim3((FXG_HIST_CAP + FXG_BLOCK - 1) / FXG_BLOCK), dim3(FXG_BLOCK), 0, c->stream,
-                           (const uint8_t *)in->bases, (u64)in->n, in->fixed_len, in->stride, (const uint8_t *)c->hist_buf[cur], (const u32 *)(c->hist_w + cur),
-                           c->hist_buf[cur ^ 1], c->hist_w + (cur ^ 1));
-        FXG_HIP(c, hipGetLastError());
+    if (fxg_hist_shortcut(in, c->hist_wcap)) {
+        FXG_LAUNCH(c, fxg_kernel_hist_fixed, (FXG_HIST_CAP + FXG_BLOCK - 1) / FXG_BLOCK, FXG_BLOCK, 0, (const uint8_t *)in->bases, (u64)in->n, in->fixed_len, in->stride,
+                   (const uint8_t *)c->hist_buf[cur], (const u32 *)(c->hist_w + cur), c->hist_buf[cur ^ 1], c->hist_w + (cur ^ 1));
+        fxg_plan_clip_from_batch(&pl, in);
     } else {
-        const u32 S2 = in->stride + 2u;
-        const u32 ntiles = (u32)((in->n + T - 1) / T), nblk = (ntiles + FXG_HIST_BLOCK - 1) / FXG_HIST_BLOCK;
-        const size_t bM = (((size_t)ntiles * S2 * 4) + 255) & ~(size_t)255, bBT = (((size_t)nblk * S2 * 4) + 255) & ~(size_t)255;
-        const size_t bExt = (((size_t)in->n * estride + 16) + 255) & ~(size_t)255, bW = (((size_t)in->n * 2) + 255) & ~(size_t)255;
-        const size_t need = bM + bBT + bExt + bW;
-        if (c->hist_ws_cap < need) {
-            FXG_HIP(c, hipStreamSynchronize(c->stream));
-            (void)hipFree(c->hist_ws);
-            c->hist_ws = nullptr; c->hist_ws_cap = 0;
-            FXG_HIP(c, hipMalloc((void **)&c->hist_ws, need + need / 8));
-            c->hist_ws_cap = need + need / 8;
-        }
-        FxgHist h;
-        h.bases = in->bases; h.len = in->len; h.fixed_len = in->fixed_len; h.stride = in->stride; h.n = in->n;
-        h.tile_reads = T; h.ntiles = ntiles;
-        h.M = (u32 *)c->hist_ws; h.BT = (u32 *)(c->hist_ws + bM);
-        h.ext = c->hist_ws + bM + bBT; h.estride = estride; h.wlen = (uint16_t *)(c->hist_ws + bM + bBT + bExt);
-        h.hist_in = c->hist_buf[cur]; h.w_in = c->hist_w + cur; h.hist_out = c->hist_buf[cur ^ 1]; h.w_out = c->hist_w + (cur ^ 1);
-        hipLaunchKernelGGL(fxg_kernel_hist_tiles, dim3(ntiles), dim3(FXG_BLOCK), 0, c->stream, h);
-        hipLaunchKernelGGL(fxg_kernel_hist_blocks, dim3(nblk), dim3(FXG_BLOCK), 0, c->stream, h);
-        hipLaunchKernelGGL(fxg_kernel_hist_top, dim3((S2 + FXG_BLOCK - 1) / FXG_BLOCK), dim3(FXG_BLOCK), 0, c->stream, h, nblk);
-        hipLaunchKernelGGL(fxg_kernel_hist_extend, dim3(ntiles), dim3(FXG_BLOCK), 0, c->stream, h);
-        FXG_HIP(c, hipGetLastError());
-        ka->clip_src = h.ext; ka->clip_stride = estride; ka->clip_total = (u64)in->n * estride; ka->wlen = h.wlen;
-        *use = 1;
+        const FxgHistWs w = fxg_hist_ws(in, pl.ka.tile_reads, estride);
+        FXG_TRY(fxg_ws_grow(c, c->hist_ws, c->hist_ws_cap, w.bytes, w.bytes + w.bytes / 8));
+        const FxgHist h = fxg_hist_args(in, pl.ka.tile_reads, estride, w, c->hist_ws, c->hist_buf[cur], c->hist_w + cur, c->hist_buf[cur ^ 1], c->hist_w + (cur ^ 1));
+        FXG_LAUNCH(c, fxg_kernel_hist_tiles, w.ntiles, FXG_BLOCK, 0, h);
+        FXG_LAUNCH(c, fxg_kernel_hist_blocks, w.nblk, FXG_BLOCK, 0, h);
+        FXG_LAUNCH(c, fxg_kernel_hist_top, (in->stride + 2u + FXG_BLOCK - 1) / FXG_BLOCK, FXG_BLOCK, 0, h, w.nblk);
+        FXG_LAUNCH(c, fxg_kernel_hist_extend, w.ntiles, FXG_BLOCK, 0, h);
+        fxg_plan_clip_from(&pl, h.ext, estride, (u64)in->n * estride, h.wlen);
     }
-    c->hist_cur = cur ^ 1;
-    if (lmax > c->hist_wcap) c->hist_wcap = lmax;
+    fxg_hist_advance(in, &c->hist_cur, &c->hist_wcap);
     return FXG_OK;
 }
 
@@ -209,21 +186,15 @@ extern "C" int fxg_run_pipeline(fxg_ctx *c, const fxg_batch *in, const fxg_param
 {
     if (!c || !in || !p || !out) return FXG_E_INVALID;
     FxgPlan pl;
-    // clip history: the DP may have to run over rows as wide as anything seen so far
-    const bool hist = c->hist_on && (p->stages & FXG_STAGE_CLIP) && in->n != 0;
-    const u32 estride = hist && c->hist_wcap > in->stride ? c->hist_wcap : in->stride;
-    const int rc = fxg_make_plan(in, p, out, &pl, c->err, sizeof c->err, hist ? estride : 0u);
-    if (rc != FXG_OK) return rc;
+    bool hist; u32 estride;
+    FXG_TRY(fxg_plan_request(in, p, out, c->hist_on != 0, c->hist_wcap, &pl, &hist, &estride, c->err, sizeof c->err));
     if (in->n == 0) {
         if (out->counters) FXG_HIP(c, hipMemsetAsync(out->counters, 0, FXG_NCOUNTERS * sizeof(u64), c->stream));
         return FXG_OK;
     }
     if (hist) {
-        int use = 0;
         FXG_HIP(c, hipSetDevice(c->device));
-        const int hrc = fxg_hist_prepass(c, in, pl.ka.tile_reads, estride, &pl.ka, &use);
-        if (hrc != FXG_OK) return hrc;
-        if (!use) { pl.ka.clip_src = in->bases; pl.ka.clip_stride = in->stride; pl.ka.clip_total = in->n * (u64)in->stride; pl.ka.wlen = nullptr; pl.lds = fxg_plan_lds(&pl); }
+        FXG_TRY(fxg_hist_prepass(c, in, estride, pl));
     }
     // what fxg_read_counters needs to do a compacting pass again, should its waits time out (fxg_fallback.h)
     c->fb_req.valid = 0;
@@ -270,27 +241,16 @@ static int fxg_launch_plan(fxg_ctx *c, FxgPlan &pl, u64 *ctr)
 
 extern "C" int fxg_run_quality_stats(fxg_ctx *c, const fxg_batch *in, uint64_t *d_hist, uint32_t hist_cols)
 {
-    if (!c || !in || !d_hist) return FXG_E_INVALID;
-    if (!in->bases || in->stride == 0 || in->stride > FXG_MAX_READ_LEN || (!in->len && (in->fixed_len == 0 || in->fixed_len > in->stride)))
-        return fxg_fail(c, FXG_E_INVALID, "quality_stats: bad batch (stride %u, fixed_len %u)", in->stride, in->fixed_len);
-    if (hist_cols < in->stride) return fxg_fail(c, FXG_E_INVALID, "quality_stats: histogram has %u columns, batch stride is %u", hist_cols, in->stride);
+    if (!c) return FXG_E_INVALID;
+    FXG_TRY(fxg_stats_check(in, d_hist, hist_cols, c->err, sizeof c->err));
     if (in->n == 0) return FXG_OK;
     FXG_HIP(c, hipSetDevice(c->device));
-    FxgStatsArgs a;
-    a.bases = in->bases; a.qual = in->qual; a.len = in->len; a.n = in->n; a.total_bytes = in->n * (u64)in->stride;
-    a.fixed_len = in->fixed_len; a.stride = in->stride; a.hist = (u64 *)d_hist; a.hist_cols = hist_cols;
     // one workgroup per CU (its LDS holds the 100 KB block histogram); fewer when the batch is small
     u64 nwg = (in->n + 255) / 256;
     if (nwg > (u64)c->cus) nwg = (u64)c->cus;
-    a.nwg = (u32)nwg;
-    const size_t need = (size_t)a.nwg * FXG_QS_PART_WORDS * sizeof(u32);
-    if (c->stats_ws_cap < need) {
-        FXG_HIP(c, hipStreamSynchronize(c->stream));
-        (void)hipFree(c->stats_ws);
-        c->stats_ws = nullptr; c->stats_ws_cap = 0;
-        FXG_HIP(c, hipMalloc((void **)&c->stats_ws, need));
-        c->stats_ws_cap = need;
-    }
+    FxgStatsArgs a = fxg_stats_args(in, d_hist, hist_cols, (u32)nwg);
+    const size_t need = (size_t)a.nwg * FXG_QS_PART_WORDS;
+    FXG_TRY(fxg_ws_grow(c, c->stats_ws, c->stats_ws_cap, need, need));
     a.partial = c->stats_ws;
     a.round_robin = 1u;
     if (const char *e = getenv("FXG_QS_ROUND_ROBIN")) a.round_robin = (u32)strtoul(e, nullptr, 0);      // measurement knob (csrc/fxg_stats.h: FxgStatsArgs::round_robin): 0 = one static slice per workgroup, tested loads; 3 = the row-strip form where the piece form would run
@@ -304,12 +264,10 @@ extern "C" int fxg_run_quality_stats(fxg_ctx *c, const fxg_batch *in, uint64_t *
         if (timed) FXG_HIP(c, hipEventRecord(c->kev0[c->kev_count % FXG_KEV_RING], c->stream));
         u32 pr = 0, pp = 0;
         // dense batches of odd length 17 .. 159: the piece form that keeps LDS block and counter half per byte, a kernel (and a register allocation) of its own
-        if (a.round_robin == 1u && (a.fixed_len & 1u) && fxg_stats_piece_plan(a, &pr, &pp)) hipLaunchKernelGGL(fxg_kernel_quality_stats_odd, dim3(a.nwg), dim3(FXG_QS_TBLOCK), lds, c->stream, a);
-        else hipLaunchKernelGGL(fxg_kernel_quality_stats, dim3(a.nwg), dim3(FXG_QS_TBLOCK), lds, c->stream, a);
-        FXG_HIP(c, hipGetLastError());
+        if (a.round_robin == 1u && (a.fixed_len & 1u) && fxg_stats_piece_plan(a, &pr, &pp)) FXG_LAUNCH(c, fxg_kernel_quality_stats_odd, a.nwg, FXG_QS_TBLOCK, lds, a);
+        else FXG_LAUNCH(c, fxg_kernel_quality_stats, a.nwg, FXG_QS_TBLOCK, lds, a);
         if (timed) { FXG_HIP(c, hipEventRecord(c->kev1[c->kev_count % FXG_KEV_RING], c->stream)); c->kev_count++; }
-        hipLaunchKernelGGL(fxg_kernel_quality_stats_fold, dim3((FXG_QS_PART_WORDS + FXG_QS_FOLD_E - 1) / FXG_QS_FOLD_E), dim3(256), 0, c->stream, a);
-        FXG_HIP(c, hipGetLastError());
+        FXG_LAUNCH(c, fxg_kernel_quality_stats_fold, (FXG_QS_PART_WORDS + FXG_QS_FOLD_E - 1) / FXG_QS_FOLD_E, 256, 0, a);
     }
     snprintf(c->last_kernel, sizeof c->last_kernel, "fxg_kernel_quality_stats");
     c->last_grid = a.nwg; c->last_block = FXG_QS_TBLOCK; c->last_lds = lds; c->last_tile = 64u * FXG_QS_UNROLL;
@@ -371,37 +329,25 @@ static int fxg_redo_without_scanner(fxg_ctx *c)
     fxg_out o2 = c->fb_req.out;
     o2.out_bases = o2.out_qual = nullptr; o2.out_len = nullptr; o2.kept_index = nullptr; o2.out_off = nullptr;
     FxgPlan pl;
-    const int prc = fxg_make_plan(&c->fb_req.in, &c->fb_req.p, &o2, &pl, c->err, sizeof c->err, c->fb_req.hist ? c->fb_req.estride : 0u);
-    if (prc != FXG_OK) return prc;
-    if (c->fb_req.hist) { pl.ka.clip_src = failed.clip_src; pl.ka.clip_stride = failed.clip_stride; pl.ka.clip_total = failed.clip_total; pl.ka.wlen = failed.wlen; pl.lds = fxg_plan_lds(&pl); }
+    FXG_TRY(fxg_make_plan(&c->fb_req.in, &c->fb_req.p, &o2, &pl, c->err, sizeof c->err, c->fb_req.hist ? c->fb_req.estride : 0u));
+    if (c->fb_req.hist) fxg_plan_clip_from(&pl, failed.clip_src, failed.clip_stride, failed.clip_total, failed.wlen);
     FXG_HIP(c, hipSetDevice(c->device));
-    const int lrc = fxg_launch_plan(c, pl, counters);
-    if (lrc != FXG_OK) return lrc;
+    FXG_TRY(fxg_launch_plan(c, pl, counters));
     // 2. + 3. block sums -> prefixes -> every kept read to its place
     FxgFbArgs f;
     f.ka = failed;                               // the arrays and folded parameters of the pass as it was asked for
     f.ka.errflag = c->errflag;
     f.nblk = (u32)((f.ka.n + FXG_FB_BLOCK - 1u) / FXG_FB_BLOCK);
     const size_t need = 2 * (size_t)f.nblk + 2;
-    if (c->fb_blk_cap < need) {
-        (void)hipFree(c->fb_blk);
-        c->fb_blk = nullptr; c->fb_blk_cap = 0;
-        FXG_HIP(c, hipMalloc((void **)&c->fb_blk, need * sizeof(u64)));
-        c->fb_blk_cap = need;
-    }
+    FXG_TRY(fxg_ws_grow(c, c->fb_blk, c->fb_blk_cap, need, need));
     f.blk = c->fb_blk;
-    hipLaunchKernelGGL(fxg_kernel_fb_sums, dim3(f.nblk), dim3(FXG_FB_BLOCK), 0, c->stream, f);
-    FXG_HIP(c, hipGetLastError());
-    hipLaunchKernelGGL(fxg_kernel_fb_scan, dim3(1), dim3(FXG_FB_BLOCK), 0, c->stream, f);
-    FXG_HIP(c, hipGetLastError());
-    if (f.ka.stages & FXG_STAGE_REVCOMP) hipLaunchKernelGGL((fxg_kernel_fb_gather<true, false>), dim3(f.nblk), dim3(FXG_FB_BLOCK), 0, c->stream, f);
-    else if (f.ka.stages & FXG_STAGE_MASK) hipLaunchKernelGGL((fxg_kernel_fb_gather<false, true>), dim3(f.nblk), dim3(FXG_FB_BLOCK), 0, c->stream, f);
-    else hipLaunchKernelGGL((fxg_kernel_fb_gather<false, false>), dim3(f.nblk), dim3(FXG_FB_BLOCK), 0, c->stream, f);
-    FXG_HIP(c, hipGetLastError());
-    if (f.ka.stages & FXG_STAGE_REVCOMP) {       // a base that has no complement: found by the gather, reported like the tile kernels do
-        hipLaunchKernelGGL(fxg_kernel_fb_errors, dim3(1), dim3(1), 0, c->stream, (const u32 *)c->errflag, counters ? counters : c->counters_scratch);
-        FXG_HIP(c, hipGetLastError());
-    }
+    FXG_LAUNCH(c, fxg_kernel_fb_sums, f.nblk, FXG_FB_BLOCK, 0, f);
+    FXG_LAUNCH(c, fxg_kernel_fb_scan, 1, FXG_FB_BLOCK, 0, f);
+    if (f.ka.stages & FXG_STAGE_REVCOMP) FXG_LAUNCH(c, (fxg_kernel_fb_gather<true, false>), f.nblk, FXG_FB_BLOCK, 0, f);
+    else if (f.ka.stages & FXG_STAGE_MASK) FXG_LAUNCH(c, (fxg_kernel_fb_gather<false, true>), f.nblk, FXG_FB_BLOCK, 0, f);
+    else FXG_LAUNCH(c, (fxg_kernel_fb_gather<false, false>), f.nblk, FXG_FB_BLOCK, 0, f);
+    // a base that has no complement: found by the gather, reported like the tile kernels do
+    if (f.ka.stages & FXG_STAGE_REVCOMP) FXG_LAUNCH(c, fxg_kernel_fb_errors, 1, 1, 0, (const u32 *)c->errflag, counters ? counters : c->counters_scratch);
     c->recoveries++;
     return FXG_OK;
 }
@@ -417,8 +363,7 @@ extern "C" int fxg_read_counters(fxg_ctx *c, const uint64_t *d_counters, uint64_
     if ((host[FXG_C_ERRORS] & FXG_DEV_ERR_SCAN_TIMEOUT) && c->fb.valid && c->fb_req.valid && src == (c->fb.counters ? c->fb.counters : c->counters_scratch) && !getenv("FXG_NO_SCAN_FALLBACK")) {
         // the launch these counters belong to gave up waiting (its workgroups were not being scheduled): the same work again without anything that waits
         c->fb.valid = 0; c->fb_req.valid = 0;
-        const int rc = fxg_redo_without_scanner(c);
-        if (rc != FXG_OK) return rc;
+        FXG_TRY(fxg_redo_without_scanner(c));
         FXG_HIP(c, hipMemcpyAsync(host, src, FXG_NCOUNTERS * sizeof(u64), hipMemcpyDeviceToHost, c->stream));
         FXG_HIP(c, hipStreamSynchronize(c->stream));
     }
@@ -440,9 +385,7 @@ extern "C" int fxg_synth_generate(fxg_ctx *c, uint64_t seed, uint64_t first, uin
     FXG_HIP(c, hipFuncSetAttribute((const void *)fxg_kernel_synth, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     const u64 blocks = (n + FXG_SYNTH_TILE - 1) / FXG_SYNTH_TILE;
     if (blocks > 0x7FFFFFFFull) return fxg_fail(c, FXG_E_INVALID, "synth: too many reads for one launch");
-    hipLaunchKernelGGL(fxg_kernel_synth, dim3((u32)blocks), dim3(FXG_BLOCK), lds, c->stream, (u64)seed, (u64)first, (u64)n, L,
-                       with_adapter, bases, qual, stride);
-    FXG_HIP(c, hipGetLastError());
+    FXG_LAUNCH(c, fxg_kernel_synth, (u32)blocks, FXG_BLOCK, lds, (u64)seed, (u64)first, (u64)n, L, with_adapter, bases, qual, stride);
     return FXG_OK;
 }
 
@@ -452,13 +395,8 @@ extern "C" int fxg_synth_generate(fxg_ctx *c, uint64_t seed, uint64_t first, uin
 static int fxg_text_reserve(fxg_ctx *c, size_t words)
 {
     if (!c->text_state) FXG_HIP(c, hipMalloc((void **)&c->text_state, sizeof(FxgTextState)));
-    if (c->text_ws_cap >= words) return FXG_OK;
-    (void)hipFree(c->text_ws);
-    c->text_ws = nullptr; c->text_ws_cap = 0;
     const size_t cap = words + words / 4 + 4096;
-    FXG_HIP(c, hipMalloc((void **)&c->text_ws, cap * sizeof(u64)));
-    c->text_ws_cap = cap;
-    return FXG_OK;
+    return fxg_ws_grow(c, c->text_ws, c->text_ws_cap, words, cap);
 }
 
 // in-place exclusive scan of data[0..n); tmp must hold the block-sum levels (n/1024 + n/1024^2 + ... + 8 words)
@@ -466,13 +404,10 @@ static int fxg_scan_u64(fxg_ctx *c, u64 *data, u64 n, u64 *tmp)
 {
     if (n == 0) return FXG_OK;
     const u64 nb = (n + FXG_SCAN_PER_BLOCK - 1) / FXG_SCAN_PER_BLOCK;
-    hipLaunchKernelGGL(fxg_kernel_scan_blocks, dim3((u32)nb), dim3(FXG_BLOCK), 0, c->stream, data, n, tmp);
-    FXG_HIP(c, hipGetLastError());
+    FXG_LAUNCH(c, fxg_kernel_scan_blocks, (u32)nb, FXG_BLOCK, 0, data, n, tmp);
     if (nb > 1) {
-        const int rc = fxg_scan_u64(c, tmp, nb, tmp + nb);
-        if (rc != FXG_OK) return rc;
-        hipLaunchKernelGGL(fxg_kernel_scan_add, dim3((u32)nb), dim3(FXG_BLOCK), 0, c->stream, data, n, (const u64 *)tmp);
-        FXG_HIP(c, hipGetLastError());
+        FXG_TRY(fxg_scan_u64(c, tmp, nb, tmp + nb));
+        FXG_LAUNCH(c, fxg_kernel_scan_add, (u32)nb, FXG_BLOCK, 0, data, n, (const u64 *)tmp);
     }
     return FXG_OK;
 }
@@ -480,83 +415,57 @@ static int fxg_scan_u64(fxg_ctx *c, u64 *data, u64 n, u64 *tmp)
 extern "C" int fxg_fastq_index(fxg_ctx *c, const uint8_t *d_text, uint64_t text_len, int at_eof, int lines_per_record, uint32_t *d_line,
                                uint64_t cap_lines, uint16_t *d_len, uint8_t *d_flags, fxg_text_info *info)
 {
-    if (!c || !d_text || !d_line || !d_len || !d_flags || !info || (lines_per_record != 4 && lines_per_record != 2)) return FXG_E_INVALID;
-    memset(info, 0, sizeof *info);
-    info->first_bad = 0xFFFFFFFFu;
+    if (!c) return FXG_E_INVALID;
+    FXG_TRY(fxg_text_index_check(d_text, text_len, lines_per_record, d_line, d_len, d_flags, info, c->err, sizeof c->err));
     if (text_len == 0) return FXG_OK;
-    if (text_len > 0xFFFFFFF0ull) return fxg_fail(c, FXG_E_INVALID, "text block too large (%llu bytes)", (unsigned long long)text_len);
     FXG_HIP(c, hipSetDevice(c->device));
     const u64 lpr = (u64)lines_per_record;
     const u64 nseg = (text_len + FXG_TEXT_SEG - 1) / FXG_TEXT_SEG;
-    int rc = fxg_text_reserve(c, (size_t)(nseg + nseg / 512 + 4096));
-    if (rc != FXG_OK) return rc;
+    FXG_TRY(fxg_text_reserve(c, (size_t)(nseg + nseg / 512 + 4096)));
     u32 *d_ls = d_line, *d_le = d_line + cap_lines;
-    FxgTextState init;
-    memset(&init, 0, sizeof init);
-    init.min_len = 0xFFFFFFFFu; init.first_bad = 0xFFFFFFFFu;
+    const FxgTextState init = fxg_text_state_init();
     FXG_HIP(c, hipMemcpyAsync(c->text_state, &init, sizeof init, hipMemcpyHostToDevice, c->stream));
     u64 *seg = c->text_ws;
-    hipLaunchKernelGGL(fxg_kernel_nl_count, dim3((u32)nseg), dim3(FXG_BLOCK), 0, c->stream, d_text, (u64)text_len, seg, c->text_state);
-    FXG_HIP(c, hipGetLastError());
+    FXG_LAUNCH(c, fxg_kernel_nl_count, (u32)nseg, FXG_BLOCK, 0, d_text, (u64)text_len, seg, c->text_state);
     // total newlines = last exclusive prefix + last count: keep the last count before the scan overwrites it
     u64 last_count = 0, last_off = 0;
     FXG_HIP(c, hipMemcpyAsync(&last_count, seg + (nseg - 1), sizeof(u64), hipMemcpyDeviceToHost, c->stream));
-    rc = fxg_scan_u64(c, seg, nseg, seg + nseg);
-    if (rc != FXG_OK) return rc;
+    FXG_TRY(fxg_scan_u64(c, seg, nseg, seg + nseg));
     FXG_HIP(c, hipMemcpyAsync(&last_off, seg + (nseg - 1), sizeof(u64), hipMemcpyDeviceToHost, c->stream));
-    hipLaunchKernelGGL(fxg_kernel_nl_scatter, dim3((u32)nseg), dim3(FXG_BLOCK), 0, c->stream, d_text, (u64)text_len, (const u64 *)seg, d_ls, d_le, (u64)cap_lines);
-    FXG_HIP(c, hipGetLastError());
+    FXG_LAUNCH(c, fxg_kernel_nl_scatter, (u32)nseg, FXG_BLOCK, 0, d_text, (u64)text_len, (const u64 *)seg, d_ls, d_le, (u64)cap_lines);
     FXG_HIP(c, hipStreamSynchronize(c->stream));
-    const u64 lines = last_off + last_count;
-    info->lines = lines;
-    u64 n = lines / lpr;
-    if (lpr * n + 1 > cap_lines) n = (cap_lines - 1) / lpr;
-    info->records = n;
-    if (n == 0) { if (at_eof && lines % lpr != 0) info->irregular |= FXG_TEXT_IRR_TAIL; return FXG_OK; }
+    const u64 lines = last_off + last_count, n = fxg_text_records(lines, lpr, cap_lines);
+    if (n == 0) { fxg_text_info_fill(info, nullptr, lines, lpr, 0, 0, text_len, at_eof); return FXG_OK; }
     const u32 grid = (u32)((n + FXG_BLOCK - 1) / FXG_BLOCK);
-    if (lines_per_record == 4) hipLaunchKernelGGL(fxg_kernel_text_records<4>, dim3(grid), dim3(FXG_BLOCK), 0, c->stream, d_text, (const u32 *)d_ls, d_le, n, d_len, d_flags, c->text_state);
-    else hipLaunchKernelGGL(fxg_kernel_text_records<2>, dim3(grid), dim3(FXG_BLOCK), 0, c->stream, d_text, (const u32 *)d_ls, d_le, n, d_len, d_flags, c->text_state);
-    FXG_HIP(c, hipGetLastError());
+    if (lines_per_record == 4) FXG_LAUNCH(c, fxg_kernel_text_records<4>, grid, FXG_BLOCK, 0, d_text, (const u32 *)d_ls, d_le, n, d_len, d_flags, c->text_state);
+    else FXG_LAUNCH(c, fxg_kernel_text_records<2>, grid, FXG_BLOCK, 0, d_text, (const u32 *)d_ls, d_le, n, d_len, d_flags, c->text_state);
     FxgTextState st;
     u32 consumed = 0;
     FXG_HIP(c, hipMemcpyAsync(&st, c->text_state, sizeof st, hipMemcpyDeviceToHost, c->stream));
     FXG_HIP(c, hipMemcpyAsync(&consumed, d_ls + lpr * n, sizeof(u32), hipMemcpyDeviceToHost, c->stream));
     FXG_HIP(c, hipStreamSynchronize(c->stream));
-    info->consumed = consumed;
-    info->max_len = st.max_len; info->min_len = st.min_len;
-    info->irregular = st.irregular;
-    info->first_bad = st.first_bad;
-    info->numeric_records = st.n_numeric;
-    info->has_cr = st.has_cr;
-    if (at_eof && (lines % lpr != 0 || consumed != text_len)) info->irregular |= FXG_TEXT_IRR_TAIL;
+    fxg_text_info_fill(info, &st, lines, lpr, n, consumed, text_len, at_eof);
     return FXG_OK;
 }
 
 extern "C" int fxg_fastq_pack(fxg_ctx *c, const uint8_t *d_text, uint64_t text_len, int lines_per_record, const uint32_t *d_line, uint64_t cap_lines,
                               const uint8_t *d_flags, uint64_t n, uint32_t stride, int qoffset, uint8_t *d_bases, uint8_t *d_qual, uint32_t *irregular)
 {
-    if (!c || !d_text || !d_line || !d_flags || !d_bases || !irregular || stride == 0 || (lines_per_record != 4 && lines_per_record != 2)) return FXG_E_INVALID;
-    *irregular = 0;
+    if (!c) return FXG_E_INVALID;
+    FXG_TRY(fxg_text_pack_check(d_text, lines_per_record, d_line, d_flags, n, stride, d_bases, d_qual, irregular, c->err, sizeof c->err));
     if (n == 0) return FXG_OK;
-    if ((((uintptr_t)d_bases | (uintptr_t)d_qual) & 15u) != 0) return fxg_fail(c, FXG_E_INVALID, "row arrays must be 16-byte aligned");
-    if (lines_per_record == 2 && d_qual) return fxg_fail(c, FXG_E_INVALID, "FASTA records have no qualities");
     FXG_HIP(c, hipSetDevice(c->device));
     const u32 *d_ls = d_line, *d_le = d_line + cap_lines;
     const u64 nchunks = (n * (u64)stride + 15) >> 4;
     u64 grid = (nchunks + FXG_BLOCK - 1) / FXG_BLOCK;
     if (grid > 65536) grid = 65536;
     FXG_HIP(c, hipMemsetAsync(&c->text_state->irregular, 0, sizeof(u32), c->stream));
-    if (lines_per_record == 4)
-        hipLaunchKernelGGL((fxg_kernel_text_pack<false, 4>), dim3((u32)grid), dim3(FXG_BLOCK), 0, c->stream, d_text, (u64)text_len, d_ls, d_le, d_flags, (u64)n, stride, qoffset, d_bases, c->text_state);
-    else
-        hipLaunchKernelGGL((fxg_kernel_text_pack<false, 2>), dim3((u32)grid), dim3(FXG_BLOCK), 0, c->stream, d_text, (u64)text_len, d_ls, d_le, d_flags, (u64)n, stride, qoffset, d_bases, c->text_state);
-    FXG_HIP(c, hipGetLastError());
+    if (lines_per_record == 4) FXG_LAUNCH(c, (fxg_kernel_text_pack<false, 4>), (u32)grid, FXG_BLOCK, 0, d_text, (u64)text_len, d_ls, d_le, d_flags, (u64)n, stride, qoffset, d_bases, c->text_state);
+    else FXG_LAUNCH(c, (fxg_kernel_text_pack<false, 2>), (u32)grid, FXG_BLOCK, 0, d_text, (u64)text_len, d_ls, d_le, d_flags, (u64)n, stride, qoffset, d_bases, c->text_state);
     if (d_qual) {
-        hipLaunchKernelGGL((fxg_kernel_text_pack<true, 4>), dim3((u32)grid), dim3(FXG_BLOCK), 0, c->stream, d_text, (u64)text_len, d_ls, d_le, d_flags, (u64)n, stride, qoffset, d_qual, c->text_state);
-        FXG_HIP(c, hipGetLastError());
+        FXG_LAUNCH(c, (fxg_kernel_text_pack<true, 4>), (u32)grid, FXG_BLOCK, 0, d_text, (u64)text_len, d_ls, d_le, d_flags, (u64)n, stride, qoffset, d_qual, c->text_state);
         // records with numeric quality lines (rare: one pass over the flags, the parse itself only where a flag is set)
-        hipLaunchKernelGGL(fxg_kernel_text_numeric, dim3((u32)((n + FXG_BLOCK - 1) / FXG_BLOCK)), dim3(FXG_BLOCK), 0, c->stream, d_text, d_ls, d_le, d_flags, (u64)n, stride, d_qual);
-        FXG_HIP(c, hipGetLastError());
+        FXG_LAUNCH(c, fxg_kernel_text_numeric, (u32)((n + FXG_BLOCK - 1) / FXG_BLOCK), FXG_BLOCK, 0, d_text, d_ls, d_le, d_flags, (u64)n, stride, d_qual);
     }
     FXG_HIP(c, hipMemcpyAsync(irregular, &c->text_state->irregular, sizeof(u32), hipMemcpyDeviceToHost, c->stream));
     FXG_HIP(c, hipStreamSynchronize(c->stream));
@@ -568,35 +477,25 @@ extern "C" int fxg_fastq_format(fxg_ctx *c, const uint8_t *d_text, int lines_per
                                 const uint64_t *d_pk_off, const uint8_t *d_rows_qual, uint32_t stride, int qoffset, int out_fasta, uint8_t *d_out,
                                 uint64_t *out_bytes)
 {
-    if (!c || !d_text || !d_line || !d_flags || !d_res || !d_out || !out_bytes || (lines_per_record != 4 && lines_per_record != 2)) return FXG_E_INVALID;
-    *out_bytes = 0;
+    if (!c) return FXG_E_INVALID;
+    FXG_TRY(fxg_text_format_check(d_text, lines_per_record, d_line, d_flags, n, d_res, d_pk_bases, d_pk_qual, d_pk_off, d_rows_qual, out_fasta, d_out, out_bytes, c->err, sizeof c->err));
     if (n == 0) return FXG_OK;
-    const bool fastq_out = lines_per_record == 4 && !out_fasta;
-    if (d_pk_bases && (!d_pk_off || (fastq_out && !d_pk_qual))) return fxg_fail(c, FXG_E_INVALID, "packed output needs bases, out_off and (FASTQ) qual");
-    if (fastq_out && !d_rows_qual) return fxg_fail(c, FXG_E_INVALID, "FASTQ output needs the batch's quality rows (numeric records are printed from them)");
     FXG_HIP(c, hipSetDevice(c->device));
-    int rc = fxg_text_reserve(c, (size_t)(n + n / 512 + 4096));
-    if (rc != FXG_OK) return rc;
+    FXG_TRY(fxg_text_reserve(c, (size_t)(n + n / 512 + 4096)));
     u64 *item = c->text_ws;
-    FxgFormatArgs a;
-    a.text = d_text; a.ls = d_line; a.le = d_line + cap_lines; a.res = d_res; a.flags = d_flags; a.item_scan = item; a.n = n;
-    a.fwd_start = fwd_start; a.rev = reverse ? 1u : 0u; a.pk_bases = d_pk_bases; a.pk_qual = d_pk_qual; a.pk_off = (const u64 *)d_pk_off;
-    a.rows_qual = d_rows_qual; a.stride = stride; a.qoffset = qoffset; a.out_fasta = out_fasta ? 1u : 0u; a.out = d_out;
+    const FxgFormatArgs a = fxg_text_format_args(d_text, d_line, cap_lines, d_flags, item, n, d_res, fwd_start, reverse, d_pk_bases, d_pk_qual, d_pk_off, d_rows_qual, stride, qoffset, out_fasta, d_out);
     const u32 nb = (u32)((n + FXG_BLOCK - 1) / FXG_BLOCK);
-    if (lines_per_record == 4) hipLaunchKernelGGL(fxg_kernel_text_sizes<4>, dim3(nb), dim3(FXG_BLOCK), 0, c->stream, a, item);
-    else hipLaunchKernelGGL(fxg_kernel_text_sizes<2>, dim3(nb), dim3(FXG_BLOCK), 0, c->stream, a, item);
-    FXG_HIP(c, hipGetLastError());
+    if (lines_per_record == 4) FXG_LAUNCH(c, fxg_kernel_text_sizes<4>, nb, FXG_BLOCK, 0, a, item);
+    else FXG_LAUNCH(c, fxg_kernel_text_sizes<2>, nb, FXG_BLOCK, 0, a, item);
     u64 last_item = 0, last_scan = 0;
     FXG_HIP(c, hipMemcpyAsync(&last_item, item + (n - 1), sizeof(u64), hipMemcpyDeviceToHost, c->stream));
-    rc = fxg_scan_u64(c, item, n, item + n);
-    if (rc != FXG_OK) return rc;
+    FXG_TRY(fxg_scan_u64(c, item, n, item + n));
     FXG_HIP(c, hipMemcpyAsync(&last_scan, item + (n - 1), sizeof(u64), hipMemcpyDeviceToHost, c->stream));
     const u32 fgrid = (u32)((n * 16 + FXG_BLOCK - 1) / FXG_BLOCK);
-    if (lines_per_record == 4) hipLaunchKernelGGL(fxg_kernel_text_format<4>, dim3(fgrid), dim3(FXG_BLOCK), 0, c->stream, a);
-    else hipLaunchKernelGGL(fxg_kernel_text_format<2>, dim3(fgrid), dim3(FXG_BLOCK), 0, c->stream, a);
-    FXG_HIP(c, hipGetLastError());
+    if (lines_per_record == 4) FXG_LAUNCH(c, fxg_kernel_text_format<4>, fgrid, FXG_BLOCK, 0, a);
+    else FXG_LAUNCH(c, fxg_kernel_text_format<2>, fgrid, FXG_BLOCK, 0, a);
     FXG_HIP(c, hipStreamSynchronize(c->stream));
-    *out_bytes = ((last_scan + last_item) & FXG_FMT_OFF_MASK);
+    *out_bytes = fxg_text_out_bytes(last_scan, last_item);
     return FXG_OK;
 }
 
@@ -609,8 +508,7 @@ extern "C" int fxg_fasta_weights(fxg_ctx *c, const uint8_t *d_text, const uint32
     FXG_HIP(c, hipSetDevice(c->device));
     if (!c->text_state) return fxg_fail(c, FXG_E_INVALID, "fxg_fasta_weights: index the block first");
     FXG_HIP(c, hipMemsetAsync(c->text_state->weighted, 0, sizeof c->text_state->weighted, c->stream));
-    hipLaunchKernelGGL(fxg_kernel_text_weights, dim3((u32)((n + FXG_BLOCK - 1) / FXG_BLOCK)), dim3(FXG_BLOCK), 0, c->stream, d_text, d_line, d_line + cap_lines, d_res, (u64)n, c->text_state);
-    FXG_HIP(c, hipGetLastError());
+    FXG_LAUNCH(c, fxg_kernel_text_weights, (u32)((n + FXG_BLOCK - 1) / FXG_BLOCK), FXG_BLOCK, 0, d_text, d_line, d_line + cap_lines, d_res, (u64)n, c->text_state);
     FXG_HIP(c, hipMemcpyAsync(weighted, c->text_state->weighted, 8 * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
     FXG_HIP(c, hipStreamSynchronize(c->stream));
     return FXG_OK;
@@ -623,34 +521,20 @@ extern "C" int fxg_barcode_prepare(fxg_ctx *c, const fxg_barcode_set *set)
 {
     if (!c || !set) return FXG_E_INVALID;
     c->bc_ready = 0;
-    const u32 E = set->entries, BL = set->barcode_len;
-    if (set->bins < 1 || set->bins > FXG_MAX_BARCODE_BINS) return fxg_fail(c, FXG_E_INVALID, "barcode split: %u bins (1 .. %d)", set->bins, FXG_MAX_BARCODE_BINS);
-    if (BL > FXG_MAX_BARCODE || (E > 0 && BL == 0)) return fxg_fail(c, FXG_E_INVALID, "barcode length %u (1 .. %d)", BL, FXG_MAX_BARCODE);
-    if (E > 0 && (!set->bases || !set->len || !set->bin)) return fxg_fail(c, FXG_E_INVALID, "barcode table without bases / lengths / bins");
-    FxgBcEntry *tab = (FxgBcEntry *)calloc(E ? E : 1, sizeof(FxgBcEntry));
+    const u32 E = set->entries;
+    const size_t room = E ? E : 1;
+    FXG_TRY(fxg_bc_set_check(set, c->err, sizeof c->err));
+    FxgBcEntry *tab = (FxgBcEntry *)calloc(room, sizeof(FxgBcEntry));
     if (!tab) return FXG_E_NOMEM;
-    for (u32 k = 0; k < E; ++k) {
-        const u32 L = set->len[k];
-        if (L > BL || set->bin[k] >= set->bins) { free(tab); return fxg_fail(c, FXG_E_INVALID, "barcode entry %u: length %u, bin %u", k, L, set->bin[k]); }
-        if (!fxg_bc_encode_entry(set->bases + (size_t)k * FXG_MAX_BARCODE, L, BL, set->bin[k], tab[k])) {
-            free(tab);
-            return fxg_fail(c, FXG_E_INVALID, "barcode entry %u: a base that is not A, C, G or T", k);
-        }
-    }
-    int rc = FXG_OK;
-    if (hipSetDevice(c->device) != hipSuccess) rc = fxg_fail(c, FXG_E_HIP, "hipSetDevice failed");
-    if (rc == FXG_OK && c->bc_tab_cap < (size_t)(E ? E : 1)) {
-        (void)hipFree(c->bc_tab);
-        c->bc_tab = nullptr; c->bc_tab_cap = 0;
-        if (hipMalloc((void **)&c->bc_tab, (size_t)(E ? E : 1) * sizeof(FxgBcEntry)) != hipSuccess) rc = fxg_fail(c, FXG_E_HIP, "hipMalloc of the barcode table failed");
-        else c->bc_tab_cap = E ? E : 1;
-    }
+    int rc = fxg_bc_set_encode(set, tab, c->err, sizeof c->err);
+    if (rc == FXG_OK && hipSetDevice(c->device) != hipSuccess) rc = fxg_fail(c, FXG_E_HIP, "hipSetDevice failed");
+    if (rc == FXG_OK) rc = fxg_ws_grow(c, c->bc_tab, c->bc_tab_cap, room, room);      // (its own message: the wait for the stream or the allocation)
     if (rc == FXG_OK && E > 0 && (hipMemcpyAsync(c->bc_tab, tab, (size_t)E * sizeof(FxgBcEntry), hipMemcpyHostToDevice, c->stream) != hipSuccess ||
                                   hipStreamSynchronize(c->stream) != hipSuccess))
         rc = fxg_fail(c, FXG_E_HIP, "upload of the barcode table failed");
     free(tab);
     if (rc != FXG_OK) return rc;
-    c->bc_entries = E; c->bc_len = BL; c->bc_mm = set->mismatches; c->bc_eol = set->eol ? 1u : 0u; c->bc_bins = set->bins;
+    c->bc_entries = E; c->bc_len = set->barcode_len; c->bc_mm = set->mismatches; c->bc_eol = set->eol ? 1u : 0u; c->bc_bins = set->bins;
     c->bc_ready = 1;
     return FXG_OK;
 }
@@ -658,30 +542,18 @@ extern "C" int fxg_barcode_prepare(fxg_ctx *c, const fxg_barcode_set *set)
 extern "C" int fxg_barcode_split(fxg_ctx *c, const uint8_t *d_text, uint64_t text_len, int lines_per_record, const uint32_t *d_line, uint64_t cap_lines,
                                  uint64_t n, uint16_t *d_rec_bin, uint8_t *d_out, uint64_t *bin_bytes, uint64_t *bin_records)
 {
-    if (!c || !d_text || !d_line || !bin_bytes || !bin_records || (lines_per_record != 4 && lines_per_record != 2)) return FXG_E_INVALID;
-    if (!c->bc_ready) return fxg_fail(c, FXG_E_INVALID, "fxg_barcode_split: no table (fxg_barcode_prepare)");
-    const u32 bins = c->bc_bins;
-    memset(bin_bytes, 0, bins * sizeof(uint64_t));
-    memset(bin_records, 0, bins * sizeof(uint64_t));
+    if (!c) return FXG_E_INVALID;
+    const u32 bins = c->bc_ready ? c->bc_bins : 0u;
+    FXG_TRY(fxg_bc_split_check(bins, d_text, text_len, lines_per_record, d_line, cap_lines, n, d_out, bin_bytes, bin_records, c->err, sizeof c->err));
     if (n == 0) return FXG_OK;
-    if (!d_out) return FXG_E_INVALID;
-    if (((uintptr_t)d_text & 3u) != 0) return fxg_fail(c, FXG_E_INVALID, "fxg_barcode_split: the text must be 4-byte aligned");
-    if (text_len > 0xFFFFFFF0ull) return fxg_fail(c, FXG_E_INVALID, "text block too large (%llu bytes)", (unsigned long long)text_len);
-    if ((u64)lines_per_record * n + 1 > cap_lines) return fxg_fail(c, FXG_E_INVALID, "fxg_barcode_split: %llu records need more than %llu lines",
-                                                                   (unsigned long long)n, (unsigned long long)cap_lines);
     FXG_HIP(c, hipSetDevice(c->device));
     const u64 tiles = (n + FXG_BC_TILE - 1) / FXG_BC_TILE;
     if (tiles > 0xFFFFFFFFull) return fxg_fail(c, FXG_E_INVALID, "fxg_barcode_split: too many records");
     const u64 N = (u64)bins * tiles;
     const u64 levels = N / 512 + 64;                         // fxg_scan_u64's block sums: N / 1024 + N / 1024^2 + ... + 8 per level
     const u64 words = N + levels + 2 * (u64)bins + (d_rec_bin ? 0 : (n + 3) / 4);
-    if (c->bc_ws_cap < words) {
-        (void)hipFree(c->bc_ws);
-        c->bc_ws = nullptr; c->bc_ws_cap = 0;
-        const size_t cap = words + words / 4 + 4096;
-        FXG_HIP(c, hipMalloc((void **)&c->bc_ws, cap * sizeof(u64)));
-        c->bc_ws_cap = cap;
-    }
+    const size_t cap = words + words / 4 + 4096;
+    FXG_TRY(fxg_ws_grow(c, c->bc_ws, c->bc_ws_cap, words, cap));
     FxgBcArgs a;
     a.text = d_text; a.ls = d_line; a.n = n; a.lpr = (u32)lines_per_record; a.tiles = (u32)tiles;
     a.tab = c->bc_tab; a.entries = c->bc_entries; a.BL = c->bc_len; a.mismatches = c->bc_mm; a.eol = c->bc_eol; a.bins = bins;
@@ -691,12 +563,9 @@ extern "C" int fxg_barcode_split(fxg_ctx *c, const uint8_t *d_text, uint64_t tex
     a.rec_bin = d_rec_bin ? d_rec_bin : (uint16_t *)(a.totals + 2 * bins);
     a.out = d_out;
     FXG_HIP(c, hipMemsetAsync(a.totals, 0, 2 * bins * sizeof(u64), c->stream));
-    hipLaunchKernelGGL(fxg_kernel_bc_classify, dim3((u32)tiles), dim3(FXG_BC_TILE), 2 * bins * sizeof(u32), c->stream, a);
-    FXG_HIP(c, hipGetLastError());
-    const int rc = fxg_scan_u64(c, a.hist_bytes, N, tmp);
-    if (rc != FXG_OK) return rc;
-    hipLaunchKernelGGL(fxg_kernel_bc_scatter, dim3((u32)tiles), dim3(FXG_BC_TILE), 0, c->stream, a);
-    FXG_HIP(c, hipGetLastError());
+    FXG_LAUNCH(c, fxg_kernel_bc_classify, (u32)tiles, FXG_BC_TILE, 2 * bins * sizeof(u32), a);
+    FXG_TRY(fxg_scan_u64(c, a.hist_bytes, N, tmp));
+    FXG_LAUNCH(c, fxg_kernel_bc_scatter, (u32)tiles, FXG_BC_TILE, 0, a);
     FXG_HIP(c, hipMemcpyAsync(bin_bytes, a.totals, bins * sizeof(u64), hipMemcpyDeviceToHost, c->stream));
     FXG_HIP(c, hipMemcpyAsync(bin_records, a.totals + bins, bins * sizeof(u64), hipMemcpyDeviceToHost, c->stream));
     FXG_HIP(c, hipStreamSynchronize(c->stream));

@@ -119,6 +119,36 @@ FXG_HD void fxg_hist_extend_column(const FxgHist &h, u32 tile, u32 x)
 
 FXG_HD u32 fxg_hist_columns(const FxgHist &h) { return h.estride > h.stride + 1u ? h.estride : h.stride + 1u; }
 
+// ---- host side of the pre-pass, one copy for the engine and tests/emu ----
+// a fixed-length batch that cannot see a stale tail (nothing longer before it): only the buffer moves on, the clip kernel reads the batch itself
+static inline bool fxg_hist_shortcut(const fxg_batch *in, u32 wcap) { return !in->len && wcap <= in->fixed_len; }
+struct FxgHistWs { u32 ntiles, nblk; size_t bM, bBT, bExt, bW, bytes; };      // the full pre-pass' workspace: M, BT, ext, wlen, each rounded up to 256 bytes
+static inline FxgHistWs fxg_hist_ws(const fxg_batch *in, u32 T, u32 estride)
+{
+    const size_t S2 = in->stride + 2u, r = 255;
+    FxgHistWs w;
+    w.ntiles = (u32)((in->n + T - 1) / T); w.nblk = (w.ntiles + FXG_HIST_BLOCK - 1) / FXG_HIST_BLOCK;
+    w.bM = (w.ntiles * S2 * 4 + r) & ~r; w.bBT = (w.nblk * S2 * 4 + r) & ~r; w.bExt = ((size_t)in->n * estride + 16 + r) & ~r; w.bW = ((size_t)in->n * 2 + r) & ~r;
+    w.bytes = w.bM + w.bBT + w.bExt + w.bW;
+    return w;
+}
+// the pre-pass' arguments over a workspace of w.bytes at `ws`, from the buffer / width pair the last batch left to the pair this one leaves
+static inline FxgHist fxg_hist_args(const fxg_batch *in, u32 T, u32 estride, const FxgHistWs &w, uint8_t *ws, const uint8_t *hist_in, const u32 *w_in, uint8_t *hist_out, u32 *w_out)
+{
+    FxgHist h;
+    h.bases = in->bases; h.len = in->len; h.fixed_len = in->fixed_len; h.stride = in->stride; h.n = in->n; h.tile_reads = T; h.ntiles = w.ntiles;
+    h.M = (u32 *)ws; h.BT = (u32 *)(ws + w.bM); h.ext = ws + w.bM + w.bBT; h.estride = estride; h.wlen = (uint16_t *)(ws + w.bM + w.bBT + w.bExt);
+    h.hist_in = hist_in; h.w_in = w_in; h.hist_out = hist_out; h.w_out = w_out;
+    return h;
+}
+// after either form: the other buffer is current, and the host's bound of the width has seen this batch
+static inline void fxg_hist_advance(const fxg_batch *in, int *cur, u32 *wcap)
+{
+    const u32 lmax = in->len ? in->stride : in->fixed_len;
+    *cur ^= 1;
+    if (lmax > *wcap) *wcap = lmax;
+}
+
 #ifndef FXG_HOST_EMULATION
 __global__ __launch_bounds__(FXG_BLOCK) void fxg_kernel_hist_tiles(const FxgHist h)
 {

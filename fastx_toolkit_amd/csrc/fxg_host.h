@@ -58,7 +58,7 @@ struct fxg_ctx {
     float *clip_ck;         // fxg_clip_two_pass_k: checkpoint scratch, FxgPlan.ck_per_wg floats per workgroup
     size_t clip_ck_cap;     // in floats
     u32 *stats_ws;          // fxg_run_quality_stats: one u32 partial histogram per workgroup
-    size_t stats_ws_cap;
+    size_t stats_ws_cap;    // in u32 words
     char err[512];
     char last_kernel[96];
     u32 last_grid, last_block, last_lds, last_tile;
@@ -77,8 +77,7 @@ struct fxg_ctx {
     size_t bc_ws_cap;                   // in u64 words
 };
 
-static int fxg_fail(fxg_ctx *ctx, int code, const char *fmt, ...) __attribute__((unused));
-static int fxg_fail(fxg_ctx *ctx, int code, const char *fmt, ...)
+__attribute__((unused)) static int fxg_fail(fxg_ctx *ctx, int code, const char *fmt, ...)
 {
     if (ctx) {
         va_list ap;
@@ -95,6 +94,7 @@ static int fxg_fail(fxg_ctx *ctx, int code, const char *fmt, ...)
         if (e__ != hipSuccess)                                                                          \
             return fxg_fail(ctx, FXG_E_HIP, "%s failed: %s (%s:%d)", #call, hipGetErrorString(e__), __FILE__, __LINE__); \
     } while (0)
+#define FXG_TRY(call) do { const int rc__ = (call); if (rc__ != FXG_OK) return rc__; } while (0)
 
 // the -v report counters of a launch: the tile kernel tallied them, one tiny kernel lays them out (defined with that kernel, in fxg_engine.hip)
 #define FXG_INTERNAL __attribute__((visibility("hidden")))      /* between the engine's translation units; not part of the C-ABI */
@@ -106,9 +106,21 @@ FXG_INTERNAL int fxg_enqueue_finish_counters(fxg_ctx *c, const FxgKArgs &ka, u64
 #define FXG_CLIP_DECLARE_UNIT(K) FXG_INTERNAL int FXG_CLIP_UNIT_FN(K)(fxg_ctx *c, FxgPlan &pl, u64 *ctr);
 FXG_CLIP_FOR_UNITS(FXG_CLIP_DECLARE_UNIT)
 
-// ------------------------------------------------------------------------------------------------
+#define FXG_LAUNCH(c, kernel, grid, block, lds, ...) do { hipLaunchKernelGGL(kernel, dim3(grid), dim3(block), lds, (c)->stream, __VA_ARGS__); FXG_HIP(c, hipGetLastError()); } while (0)      // one launch on the context's stream, checked
 
-// ------------------------------------------------------------------------------------------------
+// A workspace that only grows: at least `need` units at p afterwards.  A block too small goes, after the work queued on the stream that may still use it, and
+// one of `cap` units (need plus the site's margin; `bytes` where that is not cap elements of T) takes its place: p and have are null / 0 if that allocation fails.  *fresh: the block is new.
+template <typename T>
+static int fxg_ws_grow(fxg_ctx *c, T *&p, size_t &have, size_t need, size_t cap, bool *fresh = nullptr, size_t bytes = 0)
+{
+    if (fresh) *fresh = have < need;
+    if (have >= need) return FXG_OK;
+    if (p) FXG_HIP(c, hipStreamSynchronize(c->stream));
+    (void)hipFree(p); p = nullptr; have = 0;
+    FXG_HIP(c, hipMalloc((void **)&p, bytes ? bytes : cap * sizeof(T)));
+    have = cap;
+    return FXG_OK;
+}
 
 // dynamic-LDS attribute and occupancy of a kernel: asked once per (kernel, LDS size), not per launch
 template <typename K>
@@ -141,8 +153,7 @@ static int fxg_launch_tiles(fxg_ctx *c, K kernel, const char *kname, FxgKArgs &k
 {
     FXG_HIP(c, hipSetDevice(c->device));
     int per_cu = 0;
-    const int frc = fxg_kernel_fit(c, kernel, kname, lds, &per_cu, block);
-    if (frc != FXG_OK) return frc;
+    FXG_TRY(fxg_kernel_fit(c, kernel, kname, lds, &per_cu, block));
     // Tiles are dispensed by ticket, so nothing depends on every workgroup being resident: fill the chip.
     const int most = block == 64u ? 16 : 8;      // single-wave workgroups (fxg_rows.h, the two-pass clip instances): the LDS allows sixteen per CU
     int use = per_cu > most ? most : per_cu;
@@ -158,14 +169,8 @@ static int fxg_launch_tiles(fxg_ctx *c, K kernel, const char *kname, FxgKArgs &k
 
     if (ka.compact) {
         bool fresh = false;
-        if (c->status_cap < ka.ntiles) {
-            (void)hipFree(c->status);
-            c->status = nullptr; c->status_cap = 0;
-            size_t cap = (size_t)ka.ntiles + (size_t)ka.ntiles / 4 + 1024;
-            FXG_HIP(c, hipMalloc((void **)&c->status, FXG_STATUS_WORDS(cap) * sizeof(u64)));
-            c->status_cap = cap;
-            fresh = true;
-        }
+        const size_t cap = (size_t)ka.ntiles + (size_t)ka.ntiles / 4 + 1024;
+        FXG_TRY(fxg_ws_grow(c, c->status, c->status_cap, ka.ntiles, cap, &fresh, FXG_STATUS_WORDS(cap) * sizeof(u64)));
         // granules carry the launch's epoch, so the arrays are only cleared when they are new or the 8-bit epoch wraps
         c->epoch = c->epoch >= 255u ? 1u : c->epoch + 1u;
         if (fresh || c->epoch == 1u) FXG_HIP(c, hipMemsetAsync(c->status, 0, FXG_STATUS_WORDS(c->status_cap) * sizeof(u64), c->stream));
@@ -177,12 +182,7 @@ static int fxg_launch_tiles(fxg_ctx *c, K kernel, const char *kname, FxgKArgs &k
     ka.clip_ck = nullptr;
     if (ck_per_wg) {                             // checkpoint rows of the two-pass clipper (fxg_clip_two_pass_k): written and read by the same thread
         const size_t need = (size_t)grid * (size_t)ck_per_wg;
-        if (c->clip_ck_cap < need) {
-            (void)hipFree(c->clip_ck);
-            c->clip_ck = nullptr; c->clip_ck_cap = 0;
-            FXG_HIP(c, hipMalloc((void **)&c->clip_ck, need * sizeof(float)));
-            c->clip_ck_cap = need;
-        }
+        FXG_TRY(fxg_ws_grow(c, c->clip_ck, c->clip_ck_cap, need, need));
         ka.clip_ck = c->clip_ck;
     }
 #if defined(FXG_ABLATION) || defined(FXG_DBG_BITS)
@@ -207,10 +207,9 @@ static int fxg_launch_tiles(fxg_ctx *c, K kernel, const char *kname, FxgKArgs &k
     }
 
     if (c->profiling) FXG_HIP(c, hipEventRecord(c->kev0[c->kev_count % FXG_KEV_RING], c->stream));
-    hipLaunchKernelGGL(kernel, dim3((u32)grid), dim3(block), lds, c->stream, ka);
-    FXG_HIP(c, hipGetLastError());
+    FXG_LAUNCH(c, kernel, (u32)grid, block, lds, ka);
     if (c->profiling) { FXG_HIP(c, hipEventRecord(c->kev1[c->kev_count % FXG_KEV_RING], c->stream)); c->kev_count++; }
-    { const int frc2 = fxg_enqueue_finish_counters(c, ka, counters); if (frc2 != FXG_OK) return frc2; }      // -v report counters: the tile kernel tallied them; one tiny kernel lays them out
+    FXG_TRY(fxg_enqueue_finish_counters(c, ka, counters));      // -v report counters: the tile kernel tallied them; one tiny kernel lays them out
     snprintf(c->last_kernel, sizeof c->last_kernel, "%s", kname);
     c->last_grid = (u32)grid; c->last_block = block; c->last_lds = lds; c->last_tile = ka.tile_reads;
     return FXG_OK;

@@ -1,5 +1,6 @@
-// fxg_plan.h -- host-side validation of a request and folding of the tool parameters into launch
-// arguments.  Shared by the engine (fxg_engine.hip) and by the CPU emulator used in tests/emu.
+// fxg_plan.h -- host side of fxg_run_pipeline: validation of a request, folding of the tool parameters into launch arguments, the clip-history
+// decision and the clip source of a plan.  The engine (fxg_engine.hip) and the CPU emulator (tests/emu) compile this one copy; the host-only steps
+// of the other entry points sit in their family headers (fxg_history.h, fxg_stats.h, fxg_text.h, fxg_barcode.h) in the same way.
 #pragma once
 #include <cstdio>
 #include <cstdlib>
@@ -50,8 +51,6 @@ static inline FxgLds fxg_plan_layout(const FxgPlan *pl)
          : pl->artifacts ? fxg_lds_layout(ka.tile_reads, ka.stride, 4u, 0u) : fxg_lds_layout(ka.tile_reads, ka.stride, 0u, 0u);
 }
 static inline u32 fxg_plan_lds(const FxgPlan *pl) { return fxg_plan_layout(pl).total; }
-
-#define FXG_PLAN_FAIL(...) do { snprintf(err, cap, __VA_ARGS__); return FXG_E_INVALID; } while (0)
 
 // clip_stride: row stride of the array the clipper's DP reads when it is not the batch itself (clip history), else 0
 static inline int fxg_make_plan(const fxg_batch *in, const fxg_params *p, const fxg_out *out, FxgPlan *pl, char *err, size_t cap, u32 clip_stride = 0)
@@ -216,4 +215,23 @@ static inline int fxg_make_plan(const fxg_batch *in, const fxg_params *p, const 
     }
     pl->lds = pl->rows_nw ? fxg_rows_lds(ka.stride, (u32)pl->rows_h, (u32)pl->rows_r) : fxg_plan_lds(pl);
     return FXG_OK;
+}
+
+// The clip stage reads its queries from `src` (rows of `stride` bytes, `total` in all; wlen: the rows' DP widths or null), not from where the plan was made for.
+static inline void fxg_plan_clip_from(FxgPlan *pl, const uint8_t *src, u32 stride, u64 total, const uint16_t *wlen)
+{
+    pl->ka.clip_src = src; pl->ka.clip_stride = stride; pl->ka.clip_total = total; pl->ka.wlen = wlen;
+    pl->lds = fxg_plan_lds(pl);
+}
+// ... from the batch itself after all (a plan made for extended queries whose batch turned out not to need them)
+static inline void fxg_plan_clip_from_batch(FxgPlan *pl, const fxg_batch *in) { fxg_plan_clip_from(pl, in->bases, in->stride, in->n * (u64)in->stride, nullptr); }
+
+// The plan of a request on a context whose clip history is on or off (hist_wcap: the widest row so far).  *hist: this batch goes through the
+// history pre-pass (fxg_history.h), whose extended queries have rows of *estride bytes: the DP may have to run over rows as wide as anything seen so far.
+static inline int fxg_plan_request(const fxg_batch *in, const fxg_params *p, const fxg_out *out, bool hist_on, u32 hist_wcap, FxgPlan *pl, bool *hist, u32 *estride,
+                                   char *err, size_t cap)
+{
+    *hist = hist_on && (p->stages & FXG_STAGE_CLIP) && in->n != 0;
+    *estride = *hist && hist_wcap > in->stride ? hist_wcap : in->stride;
+    return fxg_make_plan(in, p, out, pl, err, cap, *hist ? *estride : 0u);
 }

@@ -59,6 +59,24 @@ struct FxgStatsArgs {
     u32  hist_cols;
 };
 
+// ---- host side of fxg_run_quality_stats, one copy for the engine and tests/emu ----
+static inline int fxg_stats_check(const fxg_batch *in, const uint64_t *hist, u32 hist_cols, char *err, size_t cap)
+{
+    if (!in || !hist) return FXG_E_INVALID;
+    if (!in->bases || in->stride == 0 || in->stride > FXG_MAX_READ_LEN || (!in->len && (in->fixed_len == 0 || in->fixed_len > in->stride)))
+        FXG_PLAN_FAIL("quality_stats: bad batch (stride %u, fixed_len %u)", in->stride, in->fixed_len);
+    if (hist_cols < in->stride) FXG_PLAN_FAIL("quality_stats: histogram has %u columns, batch stride is %u", hist_cols, in->stride);
+    return FXG_OK;
+}
+// the launch arguments of a checked request over `nwg` workgroups; partial, round_robin and strip0 are the caller's
+static inline FxgStatsArgs fxg_stats_args(const fxg_batch *in, uint64_t *hist, u32 hist_cols, u32 nwg)
+{
+    FxgStatsArgs a = {};
+    a.bases = in->bases; a.qual = in->qual; a.len = in->len; a.n = in->n; a.total_bytes = in->n * (u64)in->stride;
+    a.fixed_len = in->fixed_len; a.stride = in->stride; a.hist = (u64 *)hist; a.hist_cols = hist_cols; a.nwg = nwg;
+    return a;
+}
+
 #ifdef FXG_HOST_EMULATION
 #define FXG_LDS_ADD(p, v) ((void)(*(p) += (v)))
 #define FXG_GLOBAL_INC64(p) ((void)(++*(p)))

@@ -553,3 +553,60 @@ __global__ __launch_bounds__(FXG_BLOCK) void fxg_kernel_text_format(const FxgFor
     if (r < a.n) fxg_text_format_record<LPR>(a, r, threadIdx.x & 15u);
 }
 #endif  // FXG_HOST_EMULATION
+
+// ---- host side of fxg_fastq_index / _pack / _format, one copy for the engine and tests/emu: what is refused, and what the results are made of ----
+static inline FxgTextState fxg_text_state_init(void) { FxgTextState st = {}; st.min_len = st.first_bad = 0xFFFFFFFFu; return st; }
+// every check also leaves the outputs empty: the caller has nothing more to do for text_len == 0 / n == 0
+static inline int fxg_text_index_check(const uint8_t *text, u64 text_len, int lpr, const u32 *line, const uint16_t *len, const uint8_t *flags, fxg_text_info *info, char *err, size_t cap)
+{
+    if (!text || !line || !len || !flags || !info || !fxg_text_lpr_ok(lpr)) return FXG_E_INVALID;
+    memset(info, 0, sizeof *info);
+    info->first_bad = 0xFFFFFFFFu;
+    return fxg_text_check_len(text_len, err, cap);
+}
+// whole records among `lines` lines, as many as the line array has room for (one entry more than lines: the end of the last record)
+static inline u64 fxg_text_records(u64 lines, u64 lpr, u64 cap_lines) { const u64 n = lines / lpr; return lpr * n + 1 > cap_lines ? (cap_lines - 1) / lpr : n; }
+// the info of an indexed block; without a record (st may be null) only the counts and the tail rule of the lines
+static inline void fxg_text_info_fill(fxg_text_info *info, const FxgTextState *st, u64 lines, u64 lpr, u64 records, u64 consumed, u64 text_len, int at_eof)
+{
+    bool tail = lines % lpr != 0;
+    info->lines = lines; info->records = records;
+    if (records) {
+        info->consumed = consumed; info->max_len = st->max_len; info->min_len = st->min_len; info->irregular = st->irregular;
+        info->first_bad = st->first_bad; info->numeric_records = st->n_numeric; info->has_cr = st->has_cr;
+        tail = tail || consumed != text_len;
+    }
+    if (at_eof && tail) info->irregular |= FXG_TEXT_IRR_TAIL;
+}
+static inline int fxg_text_pack_check(const uint8_t *text, int lpr, const u32 *line, const uint8_t *flags, u64 n, u32 stride, const uint8_t *bases, const uint8_t *qual, u32 *irregular, char *err, size_t cap)
+{
+    if (!text || !line || !flags || !bases || !irregular || stride == 0 || !fxg_text_lpr_ok(lpr)) return FXG_E_INVALID;
+    *irregular = 0;
+    if (n == 0) return FXG_OK;
+    if ((((uintptr_t)bases | (uintptr_t)qual) & 15u) != 0) FXG_PLAN_FAIL("row arrays must be 16-byte aligned");
+    if (lpr == 2 && qual) FXG_PLAN_FAIL("FASTA records have no qualities");
+    return FXG_OK;
+}
+static inline int fxg_text_format_check(const uint8_t *text, int lpr, const u32 *line, const uint8_t *flags, u64 n, const u32 *res, const uint8_t *pk_bases, const uint8_t *pk_qual,
+                                        const uint64_t *pk_off, const uint8_t *rows_qual, int out_fasta, const uint8_t *out, uint64_t *out_bytes, char *err, size_t cap)
+{
+    if (!text || !line || !flags || !res || !out || !out_bytes || !fxg_text_lpr_ok(lpr)) return FXG_E_INVALID;
+    *out_bytes = 0;
+    if (n == 0) return FXG_OK;
+    const bool fastq_out = lpr == 4 && !out_fasta;
+    if (pk_bases && (!pk_off || (fastq_out && !pk_qual))) FXG_PLAN_FAIL("packed output needs bases, out_off and (FASTQ) qual");
+    if (fastq_out && !rows_qual) FXG_PLAN_FAIL("FASTQ output needs the batch's quality rows (numeric records are printed from them)");
+    return FXG_OK;
+}
+// the arguments of the two format kernels over an item array of n words (and the scan's levels behind them)
+static inline FxgFormatArgs fxg_text_format_args(const uint8_t *text, const u32 *line, u64 cap_lines, const uint8_t *flags, const u64 *item, u64 n, const u32 *res, u32 fwd_start, int reverse,
+                                                 const uint8_t *pk_bases, const uint8_t *pk_qual, const uint64_t *pk_off, const uint8_t *rows_qual, u32 stride, int qoffset, int out_fasta, uint8_t *out)
+{
+    FxgFormatArgs a;
+    a.text = text; a.ls = line; a.le = line + cap_lines; a.res = res; a.flags = flags; a.item_scan = item; a.n = n;
+    a.fwd_start = fwd_start; a.rev = reverse ? 1u : 0u; a.pk_bases = pk_bases; a.pk_qual = pk_qual; a.pk_off = (const u64 *)pk_off;
+    a.rows_qual = rows_qual; a.stride = stride; a.qoffset = qoffset; a.out_fasta = out_fasta ? 1u : 0u; a.out = out;
+    return a;
+}
+// bytes written: the last record's scanned item (the offset in the low bits) plus its own
+static inline u64 fxg_text_out_bytes(u64 last_scan, u64 last_item) { return (last_scan + last_item) & FXG_FMT_OFF_MASK; }

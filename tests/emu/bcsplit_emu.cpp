@@ -10,15 +10,14 @@
 struct fxg_emu_bc_table { std::vector<FxgBcEntry> tab; u32 BL, mismatches, eol, bins; };
 
 extern "C" {
-// the checks and the encoding of fxg_barcode_prepare; null on a bad table
-fxg_emu_bc_table *fxg_emu_bc_prepare(const fxg_barcode_set *set)
+// the engine's own checks and encoding of fxg_barcode_prepare; null on a refused table, with the engine's code in *rc (may be null) and its message in err
+fxg_emu_bc_table *fxg_emu_bc_prepare(const fxg_barcode_set *set, int *rc, char *err, size_t cap)
 {
-    if (!set || set->bins < 1 || set->bins > FXG_MAX_BARCODE_BINS || set->barcode_len > FXG_MAX_BARCODE || (set->entries && !set->barcode_len)) return nullptr;
     fxg_emu_bc_table *t = new fxg_emu_bc_table;
-    t->tab.resize(set->entries);
-    for (u32 k = 0; k < set->entries; ++k)
-        if (set->len[k] > set->barcode_len || set->bin[k] >= set->bins ||
-            !fxg_bc_encode_entry(set->bases + (size_t)k * FXG_MAX_BARCODE, set->len[k], set->barcode_len, set->bin[k], t->tab[k])) { delete t; return nullptr; }
+    int r = set ? fxg_bc_set_check(set, err, cap) : FXG_E_INVALID;
+    if (r == FXG_OK) { t->tab.resize(set->entries); r = fxg_bc_set_encode(set, t->tab.data(), err, cap); }
+    if (rc) *rc = r;
+    if (r != FXG_OK) { delete t; return nullptr; }
     t->BL = set->barcode_len; t->mismatches = set->mismatches; t->eol = set->eol ? 1u : 0u; t->bins = set->bins;
     return t;
 }
@@ -28,14 +27,11 @@ void fxg_emu_bc_free(fxg_emu_bc_table *t) { delete t; }
 // fxg_barcode_split over host memory: classify (one record at a time: the tile histograms, the bins' totals), the exclusive scan over
 // (bin, tile), the scatter (rank inside the tile, then the copy by 16 lanes, lane by lane)
 int fxg_emu_bc_split(const fxg_emu_bc_table *t, const uint8_t *text, uint64_t text_len, int lpr, const uint32_t *ls, uint64_t cap_lines, uint64_t n,
-                     uint16_t *rec_bin, uint8_t *out, uint64_t *bin_bytes, uint64_t *bin_records)
+                     uint16_t *rec_bin, uint8_t *out, uint64_t *bin_bytes, uint64_t *bin_records, char *err, size_t cap)
 {
-    (void)text_len;
-    const u32 bins = t->bins;
-    memset(bin_bytes, 0, bins * sizeof(uint64_t));
-    memset(bin_records, 0, bins * sizeof(uint64_t));
-    if (n == 0) return 0;
-    if ((u64)lpr * n + 1 > cap_lines || ((uintptr_t)text & 3u)) return FXG_E_INVALID;
+    const u32 bins = t ? t->bins : 0u;
+    const int rc = fxg_bc_split_check(bins, text, text_len, lpr, ls, cap_lines, n, out, bin_bytes, bin_records, err, cap);
+    if (rc != FXG_OK || n == 0) return rc;
     const u64 tiles = (n + FXG_BC_TILE - 1) / FXG_BC_TILE;
     std::vector<u64> hb(bins * tiles, 0);
     std::vector<uint16_t> own(rec_bin ? 0 : n);

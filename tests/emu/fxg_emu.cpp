@@ -1,11 +1,15 @@
-// fxg_emu.cpp -- TEST-ONLY serial emulator of the tile kernels.
+// fxg_emu.cpp -- TEST-ONLY serial emulator of the engine's kernels.
 //
 // Compiled for the HOST only (hipcc --cuda-host-only); it runs the very same __host__ __device__
 // per-thread phase bodies the GPU kernels run (bitmap build, per-read decision incl. the clipper DP,
 // chunk gather) with threadIdx replaced by a loop, and replaces only the wave-level pieces (workgroup
-// scan, decoupled look-back) by serial prefix sums.  It lets the CPU-only test tier check the device
-// logic against the oracle without a GPU.  It is NOT part of the product and is never loaded by
-// fastx_toolkit_amd; the product path has no CPU fallback.
+// scan, decoupled look-back) by serial prefix sums.  The host half of every entry point is the engine's
+// too: what a request is refused for (code and message), the plan, the history decision and layout, the
+// statistics / format arguments, the records and the info of an indexed block come from the same functions
+// of csrc/fxg_plan.h, fxg_history.h, fxg_stats.h and fxg_text.h that fxg_engine.hip calls.  Only launches
+// against loops and hipMalloc against vectors differ (tests/request_cases.py holds the two to one table).
+// It lets the CPU-only test tier check the device logic against the oracle without a GPU.  It is NOT part
+// of the product and is never loaded by fastx_toolkit_amd; the product path has no CPU fallback.
 #include <cstdlib>
 #include <vector>
 
@@ -179,13 +183,10 @@ extern "C" int fxg_emu_clip_units(void) { return FXG_CLIP_UNITS; }
 
 // clip history (fxg_history.h): the same per-column bodies the pre-pass kernels run, serially
 struct fxg_emu_hist {
-    std::vector<uint8_t> buf[2];
+    std::vector<uint8_t> buf[2], ws;        // the aligner's buffer, twice; M, BT, ext, wlen of the last full pre-pass
     u32 w[2];
     int cur;
     u32 wcap;
-    std::vector<u32> M, BT;
-    std::vector<uint8_t> ext;
-    std::vector<uint16_t> wlen;
 };
 extern "C" fxg_emu_hist *fxg_emu_hist_new(void)
 {
@@ -196,36 +197,28 @@ extern "C" fxg_emu_hist *fxg_emu_hist_new(void)
 }
 extern "C" void fxg_emu_hist_free(fxg_emu_hist *h) { delete h; }
 
-static void emu_hist_prepass(fxg_emu_hist *hs, const fxg_batch *in, u32 T, u32 estride, FxgKArgs *ka, int *use)
+static void emu_hist_prepass(fxg_emu_hist *hs, const fxg_batch *in, u32 estride, FxgPlan &pl)
 {
-    const u32 lmax = in->len ? in->stride : in->fixed_len;
     const int cur = hs->cur;
-    *use = 0;
-    if (!in->len && hs->wcap <= in->fixed_len) {
+    if (fxg_hist_shortcut(in, hs->wcap)) {
         const u32 L = in->fixed_len;
         for (u32 x = 0; x < FXG_HIST_CAP; ++x)
             hs->buf[cur ^ 1][x] = x < L ? in->bases[(in->n - 1u) * in->stride + x] : (x == L ? (uint8_t)0 : hs->buf[cur][x]);
         hs->w[cur ^ 1] = hs->w[cur] > L ? hs->w[cur] : L;
+        fxg_plan_clip_from_batch(&pl, in);
     } else {
+        const FxgHistWs w = fxg_hist_ws(in, pl.ka.tile_reads, estride);
+        hs->ws.assign(w.bytes, 0xEE);                                  // (the device's workspace is not cleared either)
+        const FxgHist h = fxg_hist_args(in, pl.ka.tile_reads, estride, w, hs->ws.data(), hs->buf[cur].data(), &hs->w[cur], hs->buf[cur ^ 1].data(), &hs->w[cur ^ 1]);
         const u32 S2 = in->stride + 2u;
-        const u32 ntiles = (u32)((in->n + T - 1) / T), nblk = (ntiles + FXG_HIST_BLOCK - 1) / FXG_HIST_BLOCK;
-        hs->M.assign((size_t)ntiles * S2, 0); hs->BT.assign((size_t)nblk * S2, 0);
-        hs->ext.assign((size_t)in->n * estride + 16, 0xEE); hs->wlen.assign(in->n, 0);
-        FxgHist h;
-        h.bases = in->bases; h.len = in->len; h.fixed_len = in->fixed_len; h.stride = in->stride; h.n = in->n;
-        h.tile_reads = T; h.ntiles = ntiles; h.M = hs->M.data(); h.BT = hs->BT.data();
-        h.ext = hs->ext.data(); h.estride = estride; h.wlen = hs->wlen.data();
-        h.hist_in = hs->buf[cur].data(); h.w_in = &hs->w[cur]; h.hist_out = hs->buf[cur ^ 1].data(); h.w_out = &hs->w[cur ^ 1];
-        for (u32 t = 0; t < ntiles; ++t) for (u32 x = 0; x < S2; ++x) fxg_hist_tile_column(h, t, x);
-        for (u32 b = 0; b < nblk; ++b) for (u32 x = 0; x < S2; ++x) fxg_hist_block_column(h, b, x);
-        for (u32 x = 0; x < S2; ++x) fxg_hist_top_column(h, nblk, x);
+        for (u32 t = 0; t < w.ntiles; ++t) for (u32 x = 0; x < S2; ++x) fxg_hist_tile_column(h, t, x);
+        for (u32 b = 0; b < w.nblk; ++b) for (u32 x = 0; x < S2; ++x) fxg_hist_block_column(h, b, x);
+        for (u32 x = 0; x < S2; ++x) fxg_hist_top_column(h, w.nblk, x);
         const u32 ncol = fxg_hist_columns(h);
-        for (u32 t = 0; t < ntiles; ++t) for (u32 x = 0; x < ncol; ++x) fxg_hist_extend_column(h, t, x);
-        ka->clip_src = h.ext; ka->clip_stride = estride; ka->clip_total = (u64)in->n * estride; ka->wlen = h.wlen;
-        *use = 1;
+        for (u32 t = 0; t < w.ntiles; ++t) for (u32 x = 0; x < ncol; ++x) fxg_hist_extend_column(h, t, x);
+        fxg_plan_clip_from(&pl, h.ext, estride, (u64)in->n * estride, h.wlen);
     }
-    hs->cur = cur ^ 1;
-    if (lmax > hs->wcap) hs->wcap = lmax;
+    fxg_hist_advance(in, &hs->cur, &hs->wcap);
 }
 
 // what fxg_make_plan chose for the last pipeline call: the clip instance (FxgPlan.amax) and whether it runs its two-pass form with checkpoints in scratch
@@ -236,17 +229,12 @@ extern "C" void fxg_emu_last_plan_clip_global(int *on, int *tile_reads) { *on = 
 extern "C" int fxg_emu_run_pipeline_hist(const fxg_batch *in, const fxg_params *p, const fxg_out *out, char *err, size_t cap, fxg_emu_hist *hs)
 {
     FxgPlan pl;
-    const bool hist = hs && (p->stages & FXG_STAGE_CLIP) && in->n != 0;
-    const u32 estride = hist && hs->wcap > in->stride ? hs->wcap : in->stride;
-    const int rc = fxg_make_plan(in, p, out, &pl, err, cap, hist ? estride : 0u);
+    bool hist; u32 estride;
+    const int rc = fxg_plan_request(in, p, out, hs != nullptr, hs ? hs->wcap : 0u, &pl, &hist, &estride, err, cap);
     if (rc != FXG_OK) return rc;
     g_last_amax = pl.amax; g_last_two_pass = pl.ck_per_wg != 0; g_last_clip_global = (int)pl.ka.clip_global; g_last_tile = (int)pl.ka.tile_reads;
     if (in->n == 0) return FXG_OK;
-    if (hist) {
-        int use = 0;
-        emu_hist_prepass(hs, in, pl.ka.tile_reads, estride, &pl.ka, &use);
-        if (!use) { pl.ka.clip_src = in->bases; pl.ka.clip_stride = in->stride; pl.ka.clip_total = in->n * (u64)in->stride; pl.ka.wlen = nullptr; pl.lds = fxg_plan_lds(&pl); }
-    }
+    if (hist) emu_hist_prepass(hs, in, estride, pl);
     uint64_t *ctr = out->counters;
     if (pl.group_a) {
         if (pl.amax == 0) return emu_run<0, false>(pl, ctr, err, cap);
@@ -274,14 +262,11 @@ extern "C" int fxg_emu_gl_last_dword(uint64_t total, uint64_t off) { return fxg_
 static uint64_t g_qs_piece_trips = 0, g_qs_piece_moved = 0;      // trips the piece form has run since the library was loaded (the tests ask whether the form under test ran)
 extern "C" uint64_t fxg_emu_quality_stats_piece_trips(void) { return g_qs_piece_trips; }
 extern "C" uint64_t fxg_emu_quality_stats_piece_moved(void) { return g_qs_piece_moved; }      // ... whose first cut was moved onto the line grid
-extern "C" int fxg_emu_run_quality_stats(const fxg_batch *in, uint64_t *hist, uint32_t hist_cols)
+extern "C" int fxg_emu_run_quality_stats(const fxg_batch *in, uint64_t *hist, uint32_t hist_cols, char *err, size_t cap)
 {
-    if (!in || !hist || !in->bases || in->stride == 0 || hist_cols < in->stride) return FXG_E_INVALID;
-    if (in->n == 0) return FXG_OK;
-    FxgStatsArgs a;
-    a.bases = in->bases; a.qual = in->qual; a.len = in->len; a.n = in->n; a.total_bytes = in->n * (u64)in->stride;
-    a.fixed_len = in->fixed_len; a.stride = in->stride; a.hist = (u64 *)hist; a.hist_cols = hist_cols;
-    a.nwg = (u32)((in->n + 255) / 256 < 3 ? (in->n + 255) / 256 : 3);
+    const int rc = fxg_stats_check(in, hist, hist_cols, err, cap);
+    if (rc != FXG_OK || in->n == 0) return rc;
+    FxgStatsArgs a = fxg_stats_args(in, hist, hist_cols, (u32)((in->n + 255) / 256 < 3 ? (in->n + 255) / 256 : 3));
     std::vector<u32> partial((size_t)a.nwg * FXG_QS_PART_WORDS), lds(FXG_QS_LDS_WORDS);
     a.partial = partial.data();
     const u32 nstrips = (in->stride + FXG_QS_STRIP - 1) / FXG_QS_STRIP;
@@ -357,16 +342,12 @@ extern "C" int fxg_emu_run_quality_stats(const fxg_batch *in, uint64_t *hist, ui
 // the scans between the kernels (fxg_engine.hip) are serial sums here.  Same contracts as fxg_fastq_index / _pack / _format / fxg_fasta_weights.
 // ------------------------------------------------------------------------------------------------
 extern "C" int fxg_emu_fastq_index(FxgTextState *st, const uint8_t *text, uint64_t text_len, int at_eof, int lpr, uint32_t *d_line, uint64_t cap_lines,
-                                   uint16_t *d_len, uint8_t *d_flags, fxg_text_info *info)
+                                   uint16_t *d_len, uint8_t *d_flags, fxg_text_info *info, char *err, size_t cap)
 {
-    if (!text || !d_line || !d_len || !d_flags || !info || (lpr != 4 && lpr != 2)) return FXG_E_INVALID;
-    memset(info, 0, sizeof *info);
-    info->first_bad = 0xFFFFFFFFu;
-    if (text_len == 0) return FXG_OK;
-    if (text_len > 0xFFFFFFF0ull) return FXG_E_INVALID;
+    const int rc = fxg_text_index_check(text, text_len, lpr, d_line, d_len, d_flags, info, err, cap);
+    if (rc != FXG_OK || text_len == 0) return rc;
     u32 *ls = d_line, *le = d_line + cap_lines;
-    memset(st, 0, sizeof *st);
-    st->min_len = 0xFFFFFFFFu; st->first_bad = 0xFFFFFFFFu;
+    *st = fxg_text_state_init();
     const u64 nseg = (text_len + FXG_TEXT_SEG - 1) / FXG_TEXT_SEG;
     u64 j = 0;
     ls[0] = 0u;
@@ -380,12 +361,8 @@ extern "C" int fxg_emu_fastq_index(FxgTextState *st, const uint8_t *text, uint64
             fxg_text_nl_store(m, off, j, ls, le, cap_lines);
             j += (u64)__builtin_popcount(m);
         }
-    const u64 lines = j;
-    info->lines = lines;
-    u64 n = lines / (u64)lpr;
-    if ((u64)lpr * n + 1 > cap_lines) n = (cap_lines - 1) / (u64)lpr;
-    info->records = n;
-    if (n == 0) { if (at_eof && lines % (u64)lpr != 0) info->irregular |= FXG_TEXT_IRR_TAIL; return FXG_OK; }
+    const u64 lines = j, n = fxg_text_records(lines, (u64)lpr, cap_lines);
+    if (n == 0) { fxg_text_info_fill(info, nullptr, lines, (u64)lpr, 0, 0, text_len, at_eof); return FXG_OK; }
     for (u64 r = 0; r < n; ++r) {
         u32 sl = 0, fl = 0;
         const u32 irr = lpr == 4 ? fxg_text_record<4>(text, ls, le, r, st->has_cr, d_len, d_flags, &sl, &fl) : fxg_text_record<2>(text, ls, le, r, st->has_cr, d_len, d_flags, &sl, &fl);
@@ -393,20 +370,15 @@ extern "C" int fxg_emu_fastq_index(FxgTextState *st, const uint8_t *text, uint64
         if (irr) { st->irregular |= irr; if ((u32)r < st->first_bad) st->first_bad = (u32)r; }
         else { if (sl > st->max_len) st->max_len = sl; if (sl < st->min_len) st->min_len = sl; }
     }
-    info->consumed = ls[(u64)lpr * n];
-    info->max_len = st->max_len; info->min_len = st->min_len; info->irregular = st->irregular; info->first_bad = st->first_bad;
-    info->numeric_records = st->n_numeric; info->has_cr = st->has_cr;
-    if (at_eof && (lines % (u64)lpr != 0 || info->consumed != text_len)) info->irregular |= FXG_TEXT_IRR_TAIL;
+    fxg_text_info_fill(info, st, lines, (u64)lpr, n, ls[(u64)lpr * n], text_len, at_eof);
     return FXG_OK;
 }
 
 extern "C" int fxg_emu_fastq_pack(const uint8_t *text, uint64_t text_len, int lpr, const uint32_t *d_line, uint64_t cap_lines, const uint8_t *flags, uint64_t n,
-                                  uint32_t stride, int qoffset, uint8_t *bases, uint8_t *qual, uint32_t *irregular)
+                                  uint32_t stride, int qoffset, uint8_t *bases, uint8_t *qual, uint32_t *irregular, char *err, size_t cap)
 {
-    if (!text || !d_line || !flags || !bases || !irregular || stride == 0 || (lpr != 4 && lpr != 2)) return FXG_E_INVALID;
-    *irregular = 0;
-    if (n == 0) return FXG_OK;
-    if (lpr == 2 && qual) return FXG_E_INVALID;
+    const int rc = fxg_text_pack_check(text, lpr, d_line, flags, n, stride, bases, qual, irregular, err, cap);
+    if (rc != FXG_OK || n == 0) return rc;
     const u32 *ls = d_line, *le = d_line + cap_lines;
     const u64 nchunks = (n * (u64)stride + 15) >> 4;
     u32 badb = 0, badq = 0;
@@ -422,28 +394,21 @@ extern "C" int fxg_emu_fastq_pack(const uint8_t *text, uint64_t text_len, int lp
 
 extern "C" int fxg_emu_fastq_format(const uint8_t *text, int lpr, const uint32_t *d_line, uint64_t cap_lines, const uint8_t *flags, uint64_t n, const uint32_t *res,
                                     uint32_t fwd_start, int reverse, const uint8_t *pk_bases, const uint8_t *pk_qual, const uint64_t *pk_off, const uint8_t *rows_qual,
-                                    uint32_t stride, int qoffset, int out_fasta, uint8_t *out, uint64_t *out_bytes)
+                                    uint32_t stride, int qoffset, int out_fasta, uint8_t *out, uint64_t *out_bytes, char *err, size_t cap)
 {
-    if (!text || !d_line || !flags || !res || !out || !out_bytes || (lpr != 4 && lpr != 2)) return FXG_E_INVALID;
-    *out_bytes = 0;
-    if (n == 0) return FXG_OK;
-    const bool fastq_out = lpr == 4 && !out_fasta;
-    if (pk_bases && (!pk_off || (fastq_out && !pk_qual))) return FXG_E_INVALID;
-    if (fastq_out && !rows_qual) return FXG_E_INVALID;
+    const int rc = fxg_text_format_check(text, lpr, d_line, flags, n, res, pk_bases, pk_qual, pk_off, rows_qual, out_fasta, out, out_bytes, err, cap);
+    if (rc != FXG_OK || n == 0) return rc;
     std::vector<u64> item(n);
-    FxgFormatArgs a;
-    a.text = text; a.ls = d_line; a.le = d_line + cap_lines; a.res = res; a.flags = flags; a.item_scan = item.data(); a.n = n;
-    a.fwd_start = fwd_start; a.rev = reverse ? 1u : 0u; a.pk_bases = pk_bases; a.pk_qual = pk_qual; a.pk_off = (const u64 *)pk_off;
-    a.rows_qual = rows_qual; a.stride = stride; a.qoffset = qoffset; a.out_fasta = out_fasta ? 1u : 0u; a.out = out;
-    u64 run = 0;
-    for (u64 r = 0; r < n; ++r) {                               // sizes, then the exclusive scan (offset in the low 40 bits, rank above)
-        const u64 v = lpr == 4 ? fxg_text_size_record<4>(a, r) : fxg_text_size_record<2>(a, r);
+    const FxgFormatArgs a = fxg_text_format_args(text, d_line, cap_lines, flags, item.data(), n, res, fwd_start, reverse, pk_bases, pk_qual, pk_off, rows_qual, stride, qoffset, out_fasta, out);
+    u64 run = 0, last = 0;
+    for (u64 r = 0; r < n; ++r) {                               // sizes, then the exclusive scan (offset in the low bits, rank above)
+        last = lpr == 4 ? fxg_text_size_record<4>(a, r) : fxg_text_size_record<2>(a, r);
         item[r] = run;
-        run += v;
+        run += last;
     }
     for (u64 r = 0; r < n; ++r)
         for (u32 l = 0; l < 16; ++l) { if (lpr == 4) fxg_text_format_record<4>(a, r, l); else fxg_text_format_record<2>(a, r, l); }
-    *out_bytes = run & ((1ull << 40) - 1ull);
+    *out_bytes = fxg_text_out_bytes(item[n - 1], last);
     return FXG_OK;
 }
 

@@ -1,26 +1,24 @@
 // fxg_stub.cpp -- TEST-ONLY stand-in for libfxg.so so that the host C layer (fastx_toolkit_amd/host) can be exercised
 // on machines without a GPU.  It exports the same C-ABI, keeps "device" memory in host RAM and runs the kernels'
 // per-thread code through the serial emulator (fxg_emu.cpp), the device text path (fxg_text.h) included, so the tools' lanes loop,
-// block cutting and sharded runs execute as on a GPU box.  Never installed next to the product: tests put tests/emu/stub first on
+// block cutting and sharded runs execute as on a GPU box.  A refused request carries the engine's code and fxg_last_error text: the checks are the engine's own
+// (the family headers under csrc/), writing into this context's err.  Never installed next to the product: tests put tests/emu/stub first on
 // LD_LIBRARY_PATH.  The product library has no CPU path and this file is not part of it.
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 
-#include "../../include/fxg.h"
+#include "fxg_stub_ctx.h"
 
-struct fxg_emu_hist;
 extern "C" int fxg_emu_run_pipeline_hist(const fxg_batch *in, const fxg_params *p, const fxg_out *out, char *err, size_t cap, fxg_emu_hist *h);
 extern "C" fxg_emu_hist *fxg_emu_hist_new(void);
-extern "C" int fxg_emu_run_quality_stats(const fxg_batch *in, uint64_t *hist, uint32_t hist_cols);
+extern "C" int fxg_emu_run_quality_stats(const fxg_batch *in, uint64_t *hist, uint32_t hist_cols, char *err, size_t cap);
 extern "C" void fxg_emu_hist_free(fxg_emu_hist *h);
 
-extern "C" int fxg_emu_fastq_index(void *st, const uint8_t *text, uint64_t text_len, int at_eof, int lpr, uint32_t *d_line, uint64_t cap_lines, uint16_t *d_len, uint8_t *d_flags, fxg_text_info *info);
-extern "C" int fxg_emu_fastq_pack(const uint8_t *text, uint64_t text_len, int lpr, const uint32_t *d_line, uint64_t cap_lines, const uint8_t *flags, uint64_t n, uint32_t stride, int qoffset, uint8_t *bases, uint8_t *qual, uint32_t *irregular);
-extern "C" int fxg_emu_fastq_format(const uint8_t *text, int lpr, const uint32_t *d_line, uint64_t cap_lines, const uint8_t *flags, uint64_t n, const uint32_t *res, uint32_t fwd_start, int reverse, const uint8_t *pk_bases, const uint8_t *pk_qual, const uint64_t *pk_off, const uint8_t *rows_qual, uint32_t stride, int qoffset, int out_fasta, uint8_t *out, uint64_t *out_bytes);
+extern "C" int fxg_emu_fastq_index(void *st, const uint8_t *text, uint64_t text_len, int at_eof, int lpr, uint32_t *d_line, uint64_t cap_lines, uint16_t *d_len, uint8_t *d_flags, fxg_text_info *info, char *err, size_t cap);
+extern "C" int fxg_emu_fastq_pack(const uint8_t *text, uint64_t text_len, int lpr, const uint32_t *d_line, uint64_t cap_lines, const uint8_t *flags, uint64_t n, uint32_t stride, int qoffset, uint8_t *bases, uint8_t *qual, uint32_t *irregular, char *err, size_t cap);
+extern "C" int fxg_emu_fastq_format(const uint8_t *text, int lpr, const uint32_t *d_line, uint64_t cap_lines, const uint8_t *flags, uint64_t n, const uint32_t *res, uint32_t fwd_start, int reverse, const uint8_t *pk_bases, const uint8_t *pk_qual, const uint64_t *pk_off, const uint8_t *rows_qual, uint32_t stride, int qoffset, int out_fasta, uint8_t *out, uint64_t *out_bytes, char *err, size_t cap);
 extern "C" int fxg_emu_fasta_weights(const uint8_t *text, const uint32_t *d_line, uint64_t cap_lines, uint64_t n, const uint32_t *res, uint64_t weighted[8]);
-
-struct fxg_ctx { char err[512]; uint64_t scratch[FXG_NCOUNTERS]; fxg_emu_hist *hist; uint64_t text_state[16]; int device; };
 
 extern "C" {
 int fxg_abi_version(void) { return FXG_ABI_VERSION; }
@@ -52,11 +50,12 @@ int fxg_timer_start(fxg_ctx *) { return 0; }
 int fxg_timer_stop(fxg_ctx *, float *ms) { *ms = 0; return 0; }
 int fxg_run_pipeline(fxg_ctx *c, const fxg_batch *in, const fxg_params *p, const fxg_out *out)
 {
+    if (!c || !in || !p || !out) return FXG_E_INVALID;
     fxg_out o = *out;
     if (!o.counters) o.counters = c->scratch;
     return fxg_emu_run_pipeline_hist(in, p, &o, c->err, sizeof c->err, c->hist);
 }
-int fxg_run_quality_stats(fxg_ctx *, const fxg_batch *in, uint64_t *h, uint32_t cols) { return fxg_emu_run_quality_stats(in, h, cols); }
+int fxg_run_quality_stats(fxg_ctx *c, const fxg_batch *in, uint64_t *h, uint32_t cols) { return !c ? FXG_E_INVALID : fxg_emu_run_quality_stats(in, h, cols, c->err, sizeof c->err); }
 int fxg_run_qtrim_qfilter(fxg_ctx *, const fxg_batch *, int, int, int, int, int, int, int, const fxg_out *) { return FXG_E_INVALID; }
 int fxg_run_clip(fxg_ctx *, const fxg_batch *, const char *, uint32_t, int, int, uint32_t, const fxg_out *) { return FXG_E_INVALID; }
 int fxg_run_revcomp_trim(fxg_ctx *, const fxg_batch *, int, int, int, const fxg_out *) { return FXG_E_INVALID; }
@@ -69,14 +68,15 @@ int fxg_read_counters(fxg_ctx *c, const uint64_t *d, uint64_t host[FXG_NCOUNTERS
 int fxg_synth_generate(fxg_ctx *, uint64_t, uint64_t, uint64_t, uint32_t, int, uint8_t *, uint8_t *, uint32_t) { return FXG_E_INVALID; }
 int fxg_fastq_index(fxg_ctx *c, const uint8_t *t, uint64_t len, int eof, int lpr, uint32_t *line, uint64_t cap, uint16_t *l16, uint8_t *fl, fxg_text_info *info)
 {
+    if (!c) return FXG_E_INVALID;
     if (getenv("FXG_EMU_NO_TEXT")) { memset(info, 0, sizeof *info); info->irregular = FXG_TEXT_IRR_TAIL; return 0; }     // every block to the host parser
-    return fxg_emu_fastq_index(c->text_state, t, len, eof, lpr, line, cap, l16, fl, info);
+    return fxg_emu_fastq_index(c->text_state, t, len, eof, lpr, line, cap, l16, fl, info, c->err, sizeof c->err);
 }
-int fxg_fastq_pack(fxg_ctx *, const uint8_t *t, uint64_t len, int lpr, const uint32_t *line, uint64_t cap, const uint8_t *fl, uint64_t n, uint32_t stride, int qo, uint8_t *b, uint8_t *q, uint32_t *irr)
-{ return fxg_emu_fastq_pack(t, len, lpr, line, cap, fl, n, stride, qo, b, q, irr); }
-int fxg_fastq_format(fxg_ctx *, const uint8_t *t, int lpr, const uint32_t *line, uint64_t cap, const uint8_t *fl, uint64_t n, const uint32_t *res, uint32_t fs, int rev, const uint8_t *pb, const uint8_t *pq,
+int fxg_fastq_pack(fxg_ctx *c, const uint8_t *t, uint64_t len, int lpr, const uint32_t *line, uint64_t cap, const uint8_t *fl, uint64_t n, uint32_t stride, int qo, uint8_t *b, uint8_t *q, uint32_t *irr)
+{ return !c ? FXG_E_INVALID : fxg_emu_fastq_pack(t, len, lpr, line, cap, fl, n, stride, qo, b, q, irr, c->err, sizeof c->err); }
+int fxg_fastq_format(fxg_ctx *c, const uint8_t *t, int lpr, const uint32_t *line, uint64_t cap, const uint8_t *fl, uint64_t n, const uint32_t *res, uint32_t fs, int rev, const uint8_t *pb, const uint8_t *pq,
                      const uint64_t *po, const uint8_t *rq, uint32_t stride, int qo, int fa, uint8_t *out, uint64_t *nb)
-{ return fxg_emu_fastq_format(t, lpr, line, cap, fl, n, res, fs, rev, pb, pq, po, rq, stride, qo, fa, out, nb); }
+{ return !c ? FXG_E_INVALID : fxg_emu_fastq_format(t, lpr, line, cap, fl, n, res, fs, rev, pb, pq, po, rq, stride, qo, fa, out, nb, c->err, sizeof c->err); }
 int fxg_fasta_weights(fxg_ctx *, const uint8_t *t, const uint32_t *line, uint64_t cap, uint64_t n, const uint32_t *res, uint64_t *w) { return fxg_emu_fasta_weights(t, line, cap, n, res, w); }
 int fxg_device_count(void) { return emu_device_count(); }
 int fxg_device_numa_node(int device) { (void)device; const char *e = getenv("FXG_EMU_NUMA_NODE"); return e ? atoi(e) : -1; }   /* no GPU, no node; the env lets a test walk the binding code */

@@ -24,7 +24,7 @@ class Out(C.Structure):
 _CXX = ["hipcc", "--cuda-host-only", "-O2", "-std=c++17", "-ffp-contract=off", "-fPIC", "-Wno-pass-failed", "-DFXG_HOST_EMULATION"]
 _LINK = ["hipcc", "-shared", "-fPIC"]         # (objects only: with --cuda-host-only the driver would read them as sources)
 _CSRC = os.path.join(_HERE, "..", "fastx_toolkit_amd", "csrc")
-_EMU_DEPS = [os.path.join(_CSRC, f) for f in ("fxg_device.h", "fxg_clip_instances.h", "fxg_kernels.h", "fxg_plan.h", "fxg_text.h", "fxg_rows.h", "fxg_history.h", "fxg_stats.h")]
+_EMU_DEPS = [os.path.join(_EMU, "fxg_stub_ctx.h")] + [os.path.join(_CSRC, f) for f in ("fxg_device.h", "fxg_clip_instances.h", "fxg_kernels.h", "fxg_plan.h", "fxg_text.h", "fxg_rows.h", "fxg_history.h", "fxg_stats.h")]
 EMU_UNITS = 8               # fxg_emu.cpp: -DFXG_EMU_TU=0 (everything but the clipper's instances) and one per unit of clip instances (csrc/fxg_clip_instances.h; tests/test_clip_instances.py)
 
 
@@ -91,7 +91,7 @@ def lib():
         _LIB.fxg_emu_run_pipeline_hist.argtypes = [C.POINTER(Batch), C.c_void_p, C.POINTER(Out), C.c_char_p, C.c_size_t, C.c_void_p]
         _LIB.fxg_emu_hist_new.restype = C.c_void_p
         _LIB.fxg_emu_hist_free.argtypes = [C.c_void_p]
-        _LIB.fxg_emu_run_quality_stats.argtypes = [C.POINTER(Batch), C.c_void_p, C.c_uint32]
+        _LIB.fxg_emu_run_quality_stats.argtypes = [C.POINTER(Batch), C.c_void_p, C.c_uint32, C.c_char_p, C.c_size_t]
         _LIB.fxg_emu_quality_stats_piece_trips.restype = C.c_uint64
         _LIB.fxg_emu_quality_stats_piece_moved.restype = C.c_uint64
     return _LIB
@@ -191,9 +191,10 @@ def run_quality_stats(bases, qual, lens, fixed_len=None, hist=None, cols=None, g
         lens = lv
     bt = Batch(b.ctypes.data, q.ctypes.data if q is not None else None, lens.ctypes.data if lens is not None else None,
                int(fixed_len or stride), stride, n)
-    rc = lib().fxg_emu_run_quality_stats(C.byref(bt), h.ctypes.data, h.shape[0])
+    err = C.create_string_buffer(512)
+    rc = lib().fxg_emu_run_quality_stats(C.byref(bt), h.ctypes.data, h.shape[0], err, 512)
     if rc != 0:
-        raise ValueError("emu quality_stats rc=%d" % rc)
+        raise ValueError("emu quality_stats rc=%d: %s" % (rc, err.value.decode()))
     if h is not hist:
         hist[:] = h
     return hist
@@ -230,7 +231,7 @@ def fastq_index(text, at_eof=True, lpr=4, cap_records=None, guard=None):
     line, lens, flags = _alloc(2 * cap_lines, np.uint32, guard), _alloc(cap_records, np.uint16, guard), _alloc(cap_records, np.uint8, guard)
     state, info = C.create_string_buffer(256), TextInfo()
     rc = lib().fxg_emu_fastq_index(state, C.c_void_p(t.ctypes.data), C.c_uint64(len(text)), C.c_int(int(at_eof)), C.c_int(lpr),
-                                   C.c_void_p(line.ctypes.data), C.c_uint64(cap_lines), C.c_void_p(lens.ctypes.data), C.c_void_p(flags.ctypes.data), C.byref(info))
+                                   C.c_void_p(line.ctypes.data), C.c_uint64(cap_lines), C.c_void_p(lens.ctypes.data), C.c_void_p(flags.ctypes.data), C.byref(info), None, C.c_size_t(0))
     if rc != 0:
         raise ValueError("emu fastq_index rc=%d" % rc)
     return dict(text=t, text_len=len(text), lpr=lpr, line=line, cap_lines=cap_lines, lens=lens, flags=flags, info=info)
@@ -244,7 +245,7 @@ def fastq_pack(ix, n, stride, qoffset=33, want_qual=True, guard=None):
     irr = C.c_uint32()
     rc = lib().fxg_emu_fastq_pack(C.c_void_p(ix["text"].ctypes.data), C.c_uint64(ix["text_len"]), C.c_int(ix["lpr"]), C.c_void_p(ix["line"].ctypes.data),
                                   C.c_uint64(ix["cap_lines"]), C.c_void_p(ix["flags"].ctypes.data), C.c_uint64(n), C.c_uint32(stride), C.c_int(qoffset),
-                                  C.c_void_p(b.ctypes.data), C.c_void_p(q.ctypes.data if q is not None else None), C.byref(irr))
+                                  C.c_void_p(b.ctypes.data), C.c_void_p(q.ctypes.data if q is not None else None), C.byref(irr), None, C.c_size_t(0))
     if rc != 0:
         raise ValueError("emu fastq_pack rc=%d" % rc)
     return b.reshape(n, stride).copy(), (q.reshape(n, stride).copy() if q is not None else None), irr.value
@@ -261,7 +262,7 @@ def fastq_format(ix, n, res, rows_qual=None, stride=0, qoffset=33, out_fasta=Fal
     rc = lib().fxg_emu_fastq_format(C.c_void_p(ix["text"].ctypes.data), C.c_int(ix["lpr"]), C.c_void_p(ix["line"].ctypes.data), C.c_uint64(ix["cap_lines"]),
                                     C.c_void_p(ix["flags"].ctypes.data), C.c_uint64(n), C.c_void_p(r.ctypes.data), C.c_uint32(0), C.c_int(0),
                                     None, None, None, C.c_void_p(rq.ctypes.data if rq is not None else None), C.c_uint32(stride), C.c_int(qoffset),
-                                    C.c_int(int(out_fasta)), C.c_void_p(out.ctypes.data), C.byref(nb))
+                                    C.c_int(int(out_fasta)), C.c_void_p(out.ctypes.data), C.byref(nb), None, C.c_size_t(0))
     if rc != 0:
         raise ValueError("emu fastq_format rc=%d" % rc)
     return out[:nb.value].tobytes()

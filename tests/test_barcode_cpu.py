@@ -191,7 +191,7 @@ class BarcodeSet(C.Structure):
 
 
 def _obj(src, out):
-    deps = [src, FXG_H, BC_H, os.path.join(ROOT, "fastx_toolkit_amd", "csrc", "fxg_device.h")]
+    deps = [src, FXG_H, BC_H, os.path.join(EMU_DIR, "fxg_stub_ctx.h"), os.path.join(ROOT, "fastx_toolkit_amd", "csrc", "fxg_device.h")]
     if not os.path.exists(out) or os.path.getmtime(out) < max(os.path.getmtime(d) for d in deps):
         subprocess.check_call(emu_py._CXX + ["-c", src, "-o", out + ".tmp"])
         os.replace(out + ".tmp", out)
@@ -210,10 +210,10 @@ def bcdir(tmp_path_factory):
 def bcemu(bcdir):
     L = C.CDLL(os.path.join(bcdir, "libbcsplit_emu.so"))
     L.fxg_emu_bc_prepare.restype = C.c_void_p
-    L.fxg_emu_bc_prepare.argtypes = [C.POINTER(BarcodeSet)]
+    L.fxg_emu_bc_prepare.argtypes = [C.POINTER(BarcodeSet), C.c_void_p, C.c_char_p, C.c_size_t]
     L.fxg_emu_bc_free.argtypes = [C.c_void_p]
     L.fxg_emu_bc_split.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p,
-                                   C.c_void_p, C.c_void_p]
+                                   C.c_void_p, C.c_void_p, C.c_char_p, C.c_size_t]
     return L
 
 
@@ -226,7 +226,7 @@ def emu_split(L, data, lpr, ents, BL, mm, eol, bins, guard=None):
         bases[k, :len(b)] = np.frombuffer(b, dtype=np.uint8)
         lens[k], binv[k] = len(b), j
     st = BarcodeSet(bases.ctypes.data, lens.ctypes.data, binv.ctypes.data, E, BL, mm, int(eol), bins)
-    t = L.fxg_emu_bc_prepare(C.byref(st))
+    t = L.fxg_emu_bc_prepare(C.byref(st), None, None, 0)
     assert t
     ls_all = line_starts(data)
     n = (len(ls_all) - 1) // lpr
@@ -239,7 +239,7 @@ def emu_split(L, data, lpr, ents, BL, mm, eol, bins, guard=None):
     out = emu_py._alloc(total, np.uint8, guard)
     bb, br = np.zeros(bins, dtype=np.uint64), np.zeros(bins, dtype=np.uint64)
     rc = L.fxg_emu_bc_split(t, text.ctypes.data if len(data) else None, len(data), lpr, ls.ctypes.data, lpr * n + 1, n,
-                            rb.ctypes.data if n else None, out.ctypes.data if total else None, bb.ctypes.data, br.ctypes.data)
+                            rb.ctypes.data if n else None, out.ctypes.data if total else None, bb.ctypes.data, br.ctypes.data, None, 0)
     L.fxg_emu_bc_free(t)
     assert rc == 0
     return rb.astype(np.int64), bb, br, out.tobytes()
@@ -267,10 +267,10 @@ def _guard_child(where, q):
     try:
         L = C.CDLL(os.path.join(q, "libbcsplit_emu.so"))
         L.fxg_emu_bc_prepare.restype = C.c_void_p
-        L.fxg_emu_bc_prepare.argtypes = [C.POINTER(BarcodeSet)]
+        L.fxg_emu_bc_prepare.argtypes = [C.POINTER(BarcodeSet), C.c_void_p, C.c_char_p, C.c_size_t]
         L.fxg_emu_bc_free.argtypes = [C.c_void_p]
         L.fxg_emu_bc_split.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p,
-                                       C.c_void_p, C.c_void_p]
+                                       C.c_void_p, C.c_void_p, C.c_char_p, C.c_size_t]
         rng = random.Random(hash(where) & 0xFFFF)
         for k in range(12):
             BL = rng.choice([1, 7, 16, 64])
@@ -348,3 +348,70 @@ def test_tool_limits_over_stub(stubdir):
     ok = "".join("i%d %s\n" % (k, "ACGTACGT") for k in range(4095))
     code, out, err, files = run_tool(stubdir, ["--bcfile", "{B}", "--prefix", "{P}", "--bol", "--quiet"], ok, ">a\nACGTACGT\n")
     assert code == 0 and len(files) == 4096 and files["i0"] == ">a\nACGTACGT\n"
+
+
+# ---- refused requests: the table of tests/request_cases.py through the stub, whose checks are the engine's own ---------------------------
+@pytest.fixture(scope="module")
+def stub_session(stubdir):
+    import request_cases as rq
+    s = rq.Session(os.path.join(stubdir, "libfxg.so"))
+    yield s
+    s.close()
+
+
+def _case_ids():
+    import request_cases as rq
+    return [c[0] for c in rq.CASES]
+
+
+@pytest.mark.parametrize("k", range(len(_case_ids())), ids=_case_ids())
+def test_refused_requests_over_stub(stub_session, k):
+    import request_cases as rq
+    rq.refuse(stub_session, rq.CASES[k])
+
+
+def test_accepted_requests_over_stub(stub_session):
+    """one request per entry point of the table that goes through: checks that refused everything would pass the table"""
+    s, L = stub_session, stub_session.lib
+    fq = b"@a\nACGT\n+\nIIII\n"
+
+    def arr(n, dtype=np.uint8, fill=None):
+        a = emu_py._aligned(n, dtype)
+        if fill is not None:
+            a[:len(fill)] = np.frombuffer(fill, dtype=np.uint8)
+        return a
+    text, line, lens, flags = arr(len(fq) + 16, fill=fq), arr(10, np.uint32), arr(1, np.uint16), arr(1)
+    assert L.fxg_fastq_index(s.ctx, text.ctypes.data, len(fq), 1, 4, line.ctypes.data, 5, lens.ctypes.data, flags.ctypes.data, C.byref(s.info)) == 0
+    assert (s.info.records, s.info.consumed, s.info.irregular, lens[0]) == (1, len(fq), 0, 4)
+    two, line2 = arr(2 * len(fq) + 16, fill=fq + fq), arr(10, np.uint32)      # a line array with room for one record of the two: the index stops there
+    assert L.fxg_fastq_index(s.ctx, two.ctypes.data, 2 * len(fq), 0, 4, line2.ctypes.data, 5, lens.ctypes.data, flags.ctypes.data, C.byref(s.info)) == 0
+    assert (s.info.lines, s.info.records, s.info.consumed, s.info.irregular) == (8, 1, len(fq), 0)
+    bases, qual = arr(16), arr(16)
+    assert L.fxg_fastq_pack(s.ctx, text.ctypes.data, len(fq), 4, line.ctypes.data, 5, flags.ctypes.data, 1, 16, 33, bases.ctypes.data, qual.ctypes.data, C.byref(s.word)) == 0
+    assert bases[:4].tobytes() == b"ACGT" and qual[:4].tobytes() == b"IIII" and s.word.value == 0
+    res, out = arr(1, np.uint32), arr(len(fq) + 1 + 16)
+    res[0] = (1 << 16) | 4
+    assert L.fxg_fastq_format(s.ctx, text.ctypes.data, 4, line.ctypes.data, 5, flags.ctypes.data, 1, res.ctypes.data, 0, 0, None, None, None, qual.ctypes.data, 16, 33, 0,
+                              out.ctypes.data, C.byref(s.bytes_out)) == 0
+    assert out[:s.bytes_out.value].tobytes() == fq
+    hist = arr(16 * 5 * 128, np.uint64)
+    assert L.fxg_run_quality_stats(s.ctx, C.byref(rq_batch(bases, qual, 4, 16, 1)), hist.ctypes.data, 16) == 0
+    assert int(hist.sum()) == 4
+    assert L.fxg_barcode_prepare(s.ctx, s.barcodes([(b"ACGT", 0)])) == 0
+    bb, br, rb = (C.c_uint64 * 2)(), (C.c_uint64 * 2)(), arr(1, np.uint16)
+    assert L.fxg_barcode_split(s.ctx, text.ctypes.data, len(fq), 4, line.ctypes.data, 5, 1, rb.ctypes.data, out.ctypes.data, bb, br) == 0
+    assert list(br) == [1, 0] and list(bb) == [len(fq), 0] and out[:len(fq)].tobytes() == fq
+    p = s.params(0x02)                  # fastq_quality_trimmer -t 0: the one read stays whole
+    res[0] = 0
+    assert L.fxg_run_pipeline(s.ctx, C.byref(rq_batch(bases, qual, 4, 16, 1)), C.addressof(p), C.byref(rq_out(res))) == 0, s.last_error()
+    assert (int(res[0]) & 0xFFFF, (int(res[0]) >> 16) & 1) == (4, 1)
+
+
+def rq_batch(bases, qual, fixed_len, stride, n):
+    from fastx_toolkit_amd.engine import FxgBatch
+    return FxgBatch(bases.ctypes.data, qual.ctypes.data, None, fixed_len, stride, n)
+
+
+def rq_out(res):
+    from fastx_toolkit_amd.engine import FxgOut
+    return FxgOut(res=res.ctypes.data)

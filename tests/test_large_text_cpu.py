@@ -346,7 +346,7 @@ def test_sparse_index_over_the_whole_mapping(sparse):
     lens, flags = np.full(cap_records, 0xEEEE, np.uint16), np.full(cap_records, 0xEE, np.uint8)
     state, info = C.create_string_buffer(256), emu_py.TextInfo()
     rc = emu_py.lib().fxg_emu_fastq_index(state, C.c_void_p(sp.addr), C.c_uint64(lt.CAP), C.c_int(1), C.c_int(b.lpr), C.c_void_p(line.ctypes.data),
-                                          C.c_uint64(cap_lines), C.c_void_p(lens.ctypes.data), C.c_void_p(flags.ctypes.data), C.byref(info))
+                                          C.c_uint64(cap_lines), C.c_void_p(lens.ctypes.data), C.c_void_p(flags.ctypes.data), C.byref(info), None, C.c_size_t(0))
     assert rc == 0
     rr = torch.cat([b.range(r0, r1) for r0, r1 in cl])
     f = {k: v.numpy() for k, v in b.fields(rr).items()}
@@ -398,7 +398,7 @@ def _emu_pack(text_addr, text_len, lpr, line, cap_lines, flags, n, stride):
     irr = C.c_uint32()
     rc = emu_py.lib().fxg_emu_fastq_pack(C.c_void_p(text_addr), C.c_uint64(text_len), C.c_int(lpr), C.c_void_p(line.ctypes.data), C.c_uint64(cap_lines),
                                          C.c_void_p(flags.ctypes.data), C.c_uint64(n), C.c_uint32(stride), C.c_int(33), C.c_void_p(bases.ctypes.data),
-                                         C.c_void_p(qual.ctypes.data if qual is not None else None), C.byref(irr))
+                                         C.c_void_p(qual.ctypes.data if qual is not None else None), C.byref(irr), None, C.c_size_t(0))
     assert rc == 0
     return bases[:n * stride].reshape(n, stride), (qual[:n * stride].reshape(n, stride) if qual is not None else None), irr.value
 
@@ -410,7 +410,7 @@ def _emu_format(text_addr, lpr, line, cap_lines, flags, n, res, fwd, rows_qual, 
     rc = emu_py.lib().fxg_emu_fastq_format(C.c_void_p(text_addr), C.c_int(lpr), C.c_void_p(line.ctypes.data), C.c_uint64(cap_lines), C.c_void_p(flags.ctypes.data),
                                            C.c_uint64(n), C.c_void_p(r.ctypes.data), C.c_uint32(fwd), C.c_int(0), None, None, None,
                                            C.c_void_p(rows_qual.ctypes.data if rows_qual is not None else None), C.c_uint32(stride), C.c_int(33),
-                                           C.c_int(int(out_fasta)), C.c_void_p(out.ctypes.data), C.byref(nb))
+                                           C.c_int(int(out_fasta)), C.c_void_p(out.ctypes.data), C.byref(nb), None, C.c_size_t(0))
     assert rc == 0 and nb.value <= cap_out and (out[nb.value:] == 0xA5).all()
     return out[:nb.value].tobytes()
 
@@ -456,9 +456,9 @@ def bcemu(tmp_path_factory):
     subprocess.check_call(emu_py._LINK + [obj, "-o", os.path.join(d, "libbcsplit_emu.so")])
     L = C.CDLL(os.path.join(d, "libbcsplit_emu.so"))
     L.fxg_emu_bc_prepare.restype = C.c_void_p
-    L.fxg_emu_bc_prepare.argtypes = [C.POINTER(BarcodeSet)]
+    L.fxg_emu_bc_prepare.argtypes = [C.POINTER(BarcodeSet), C.c_void_p, C.c_char_p, C.c_size_t]
     L.fxg_emu_bc_free.argtypes = [C.c_void_p]
-    L.fxg_emu_bc_split.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.fxg_emu_bc_split.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_char_p, C.c_size_t]
     return L
 
 
@@ -469,12 +469,12 @@ def _emu_split(L, ents, mm, eol, bins, text_addr, text_len, lpr, ls, n, total):
         bases[k, :len(x)] = np.frombuffer(x, np.uint8)
         lens[k], binv[k] = len(x), j
     st = BarcodeSet(bases.ctypes.data, lens.ctypes.data, binv.ctypes.data, E, lt.BL, mm, int(eol), bins)
-    t = L.fxg_emu_bc_prepare(C.byref(st))
+    t = L.fxg_emu_bc_prepare(C.byref(st), None, None, 0)
     assert t
     rb, out = np.full(n + 8, 0xEEEE, np.uint16), np.full(total + 64, 0xA5, np.uint8)
     bb, br = np.zeros(bins, np.uint64), np.zeros(bins, np.uint64)
     ls = np.ascontiguousarray(ls, dtype=np.uint32)
-    rc = L.fxg_emu_bc_split(t, text_addr, text_len, lpr, ls.ctypes.data, len(ls), n, rb.ctypes.data, out.ctypes.data, bb.ctypes.data, br.ctypes.data)
+    rc = L.fxg_emu_bc_split(t, text_addr, text_len, lpr, ls.ctypes.data, len(ls), n, rb.ctypes.data, out.ctypes.data, bb.ctypes.data, br.ctypes.data, None, 0)
     L.fxg_emu_bc_free(t)
     assert rc == 0 and (rb[n:] == 0xEEEE).all() and (out[total:] == 0xA5).all()
     return rb[:n].astype(np.int64), bb, br, out[:total].tobytes()
@@ -597,7 +597,7 @@ def test_format_from_packed_arrays_past_2_24_kept_records():
     nb = C.c_uint64()
     rc = emu_py.lib().fxg_emu_fastq_format(C.c_void_p(text.ctypes.data), C.c_int(2), C.c_void_p(line.ctypes.data), C.c_uint64(cap_lines), C.c_void_p(flags.ctypes.data),
                                            C.c_uint64(n), C.c_void_p(res.ctypes.data), C.c_uint32(0), C.c_int(0), C.c_void_p(pk.ctypes.data), None, C.c_void_p(rank.ctypes.data),
-                                           None, C.c_uint32(0), C.c_int(33), C.c_int(0), C.c_void_p(out.ctypes.data), C.byref(nb))
+                                           None, C.c_uint32(0), C.c_int(33), C.c_int(0), C.c_void_p(out.ctypes.data), C.byref(nb), None, C.c_size_t(0))
     assert rc == 0 and nb.value == 4 * k and (out[4 * k:] == 0xA5).all()
     got = out[:4 * k].reshape(k, 4)
     assert (got[:, 0] == 62).all() and (got[:, 1] == 10).all() and (got[:, 3] == 10).all()
