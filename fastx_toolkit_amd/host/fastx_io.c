@@ -565,7 +565,7 @@ static int fxh_open_output(const char *filename)
 {
     if (strcmp(filename, "-") == 0) return STDOUT_FILENO;
     /* read-write where that is allowed: the many-strand run maps its one output file (fxh_strands.c); a file that may only be written still opens */
-    /* one process per GPU over one job (FXH_WORLD > 1, fxh_strands.c): the file is rank 0's to empty; the others only open it */
+    /* one process per GPU over one job (FXH_WORLD > 1, fxh_rank.c): the file is rank 0's to empty; the others only open it */
     const char *we = getenv("FXH_WORLD"), *re = getenv("FXH_RANK");
     const int trunc = (g_fxh_batch_writer && we && atoi(we) > 1 && re && atoi(re) > 0) ? 0 : O_TRUNC;
     int fd = open(filename, O_CREAT | O_RDWR | trunc, 0666);

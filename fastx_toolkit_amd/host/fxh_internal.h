@@ -1,4 +1,4 @@
-/* fxh_internal.h -- shared between fastx_io.c (record API) and the batch path (fxh_batch.c, fxh_io.c, fxh_lanes.c, fxh_parts.c). Not installed. */
+/* fxh_internal.h -- shared between fastx_io.c (record API) and the batch path (fxh_batch.c, fxh_io.c, fxh_lanes.c, fxh_parts.c, fxh_strands.c, fxh_rank.c). Not installed. */
 #ifndef FXH_INTERNAL_H
 #define FXH_INTERNAL_H
 #include <stddef.h>

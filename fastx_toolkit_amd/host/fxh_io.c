@@ -1,5 +1,5 @@
 /* fxh_io.c -- I/O overlap of the batch path: one thread reads the next block while the current one is processed, another one writes the previous
- * output while the next is being formatted (fxh_priv.h). */
+ * output while the next is being formatted; the pread loop and the task pool of the one-file run (fxh_priv.h). */
 #include "fxh_priv.h"
 int g_parts_mode;               /* a sharded run is under way (fxh_run_parts): smaller read-ahead per part */
 
@@ -18,17 +18,24 @@ static size_t fxh_count_newlines(const char *p, size_t n)
     return c;
 }
 
+/* n bytes from `off` on, less only where the file ends: the number read */
+size_t fxh_pread_full(int fd, char *dst, size_t n, off_t off)
+{
+    size_t got = 0;
+    while (got < n) {
+        const ssize_t k = pread(fd, dst + got, n - got, off + (off_t)got);
+        if (k < 0) { if (errno == EINTR) continue; err(1, "read failed"); }
+        if (k == 0) break;
+        got += (size_t)k;
+    }
+    return got;
+}
+
 typedef struct { int fd; char *dst; size_t n; off_t off; size_t got, newlines; } fxh_pread_job;
 static void *fxh_pread_main(void *arg)
 {
     fxh_pread_job *j = (fxh_pread_job *)arg;
-    j->got = 0;
-    while (j->got < j->n) {
-        ssize_t k = pread(j->fd, j->dst + j->got, j->n - j->got, j->off + (off_t)j->got);
-        if (k < 0) { if (errno == EINTR) continue; err(1, "read failed"); }
-        if (k == 0) break;
-        j->got += (size_t)k;
-    }
+    j->got = fxh_pread_full(j->fd, j->dst, j->n, j->off);
     j->newlines = fxh_count_newlines(j->dst, j->got);       /* the census the record cutter needs, while the slice is cache-warm */
     return NULL;
 }
@@ -250,18 +257,42 @@ static void fxh_prefetch_request(fxh_prefetch *pf, char *buf, size_t cap)
     pthread_mutex_unlock(&pf->mu);
 }
 
-/* Make the next block current: [unread tail of the old block | prefetched data]; hand the old buffer back to the thread. */
+/* the first block: read synchronously; 1 = there is more, the read-ahead thread runs and waits for its first request */
+static int fxh_prefetch_first(fxh_prefetch *pf, struct fxh_reader *rd)
+{
+    fxh_reader_fill(rd);
+    if (rd->eof) return 0;
+    pthread_mutex_init(&pf->mu, NULL); pthread_cond_init(&pf->cv, NULL);
+    pf->fd = rd->fd; pf->state = 0; pf->started = 1;
+    pf->gap = rd->cap / 4 < FXH_GAP_MAX ? rd->cap / 4 : FXH_GAP_MAX;
+    fxh_prefetch_probe(pf, rd->fd);
+    pf->limit = rd->limit;
+    if (pthread_create(&pf->th, NULL, fxh_prefetch_main, pf) != 0) err(1, "pthread_create");
+    return 1;
+}
+
+/* the finished block becomes the reader's: [unread tail of the old block | prefetched data].  Returns the old buffer. */
+static char *fxh_prefetch_take(fxh_prefetch *pf, struct fxh_reader *rd, size_t *newlines)
+{
+    pthread_mutex_lock(&pf->mu);
+    while (pf->state != 2) pthread_cond_wait(&pf->cv, &pf->mu);
+    pf->state = 0;
+    char *nb = pf->buf; const size_t filled = pf->filled; const int eof = pf->eof;
+    if (newlines) *newlines = pf->newlines;
+    pthread_mutex_unlock(&pf->mu);
+    const size_t tail = rd->end - rd->beg;
+    if (tail > pf->gap) errx(1, "input record longer than %zu bytes", pf->gap);
+    memcpy(nb + pf->gap - tail, rd->buf + rd->beg, tail);
+    char *old = rd->buf;
+    rd->buf = nb; rd->beg = pf->gap - tail; rd->end = pf->gap + filled; rd->eof = eof;
+    return old;
+}
+
+/* Make the next block current; hand the old buffer back to the thread. */
 void fxh_next_block(fxh_prefetch *pf, struct fxh_reader *rd, char **spare)
 {
     if (!pf->started) {                /* first block: synchronous, then start reading ahead */
-        fxh_reader_fill(rd);
-        if (!rd->eof) {
-            pthread_mutex_init(&pf->mu, NULL); pthread_cond_init(&pf->cv, NULL);
-            pf->fd = rd->fd; pf->state = 0; pf->started = 1;
-            pf->gap = rd->cap / 4 < FXH_GAP_MAX ? rd->cap / 4 : FXH_GAP_MAX;
-            fxh_prefetch_probe(pf, rd->fd);
-            pf->limit = rd->limit;
-            if (pthread_create(&pf->th, NULL, fxh_prefetch_main, pf) != 0) err(1, "pthread_create");
+        if (fxh_prefetch_first(pf, rd)) {
             *spare = (char *)malloc(rd->cap + 1);
             if (!*spare) err(1, "out of memory");
             fxh_prefetch_request(pf, *spare, rd->cap);
@@ -269,18 +300,8 @@ void fxh_next_block(fxh_prefetch *pf, struct fxh_reader *rd, char **spare)
         return;
     }
     if (rd->eof) return;               /* everything has been read already; only the tail remains in rd */
-    pthread_mutex_lock(&pf->mu);
-    while (pf->state != 2) pthread_cond_wait(&pf->cv, &pf->mu);
-    pf->state = 0;
-    char *nb = pf->buf; const size_t filled = pf->filled; const int eof = pf->eof;
-    pthread_mutex_unlock(&pf->mu);
-    const size_t tail = rd->end - rd->beg;
-    if (tail > pf->gap) errx(1, "input record longer than %zu bytes", pf->gap);
-    memcpy(nb + pf->gap - tail, rd->buf + rd->beg, tail);
-    char *old = rd->buf;
-    rd->buf = nb; rd->beg = pf->gap - tail; rd->end = pf->gap + filled; rd->eof = eof;
-    *spare = old;
-    if (!eof) fxh_prefetch_request(pf, old, rd->cap);
+    *spare = fxh_prefetch_take(pf, rd, NULL);
+    if (!rd->eof) fxh_prefetch_request(pf, *spare, rd->cap);
 }
 
 /* The same for the lanes loop, where the previous buffers may still be in use: the read-ahead for the FOLLOWING block goes
@@ -289,30 +310,12 @@ void fxh_next_block_ring(fxh_prefetch *pf, struct fxh_reader *rd, char *target, 
 {
     *fresh_newlines = (size_t)-1;      /* unknown: the caller counts */
     if (!pf->started) {                /* first block: synchronous, then start reading ahead */
-        fxh_reader_fill(rd);
-        if (!rd->eof) {
-            pthread_mutex_init(&pf->mu, NULL); pthread_cond_init(&pf->cv, NULL);
-            pf->fd = rd->fd; pf->state = 0; pf->started = 1;
-            pf->gap = rd->cap / 4 < FXH_GAP_MAX ? rd->cap / 4 : FXH_GAP_MAX;
-            fxh_prefetch_probe(pf, rd->fd);
-            pf->limit = rd->limit;
-            if (pthread_create(&pf->th, NULL, fxh_prefetch_main, pf) != 0) err(1, "pthread_create");
-            fxh_prefetch_request(pf, target, rd->cap);
-        }
+        if (fxh_prefetch_first(pf, rd)) fxh_prefetch_request(pf, target, rd->cap);
         return;
     }
     if (rd->eof) return;               /* everything has been read already; only the tail remains in rd */
-    pthread_mutex_lock(&pf->mu);
-    while (pf->state != 2) pthread_cond_wait(&pf->cv, &pf->mu);
-    pf->state = 0;
-    char *nb = pf->buf; const size_t filled = pf->filled; const int eof = pf->eof;
-    *fresh_newlines = pf->newlines;
-    pthread_mutex_unlock(&pf->mu);
-    const size_t tail = rd->end - rd->beg;
-    if (tail > pf->gap) errx(1, "input record longer than %zu bytes", pf->gap);
-    memcpy(nb + pf->gap - tail, rd->buf + rd->beg, tail);
-    rd->buf = nb; rd->beg = pf->gap - tail; rd->end = pf->gap + filled; rd->eof = eof;
-    if (!eof) fxh_prefetch_request(pf, target, rd->cap);
+    (void)fxh_prefetch_take(pf, rd, fresh_newlines);
+    if (!rd->eof) fxh_prefetch_request(pf, target, rd->cap);
 }
 
 void fxh_prefetch_stop(fxh_prefetch *pf)
@@ -352,15 +355,21 @@ void fxh_awriter_wait(fxh_awriter *aw)
     pthread_mutex_unlock(&aw->mu);
 }
 
-/* hand the writer's filled buffer to the thread and continue formatting into the other one */
-void fxh_awriter_submit(fxh_awriter *aw, struct fxh_writer *w, char **spare, size_t *spare_cap)
+/* the writer thread exists (started on first use) and has nothing pending: its other buffer is free again */
+static void fxh_awriter_ready(fxh_awriter *aw, struct fxh_writer *w)
 {
     if (!aw->started) {
         pthread_mutex_init(&aw->mu, NULL); pthread_cond_init(&aw->cv, NULL);
         aw->w = w; aw->state = 0; aw->started = 1;
         if (pthread_create(&aw->th, NULL, fxh_awriter_main, aw) != 0) err(1, "pthread_create");
     }
-    fxh_awriter_wait(aw);              /* the other buffer is free again */
+    fxh_awriter_wait(aw);
+}
+
+/* hand the writer's filled buffer to the thread and continue formatting into the other one */
+void fxh_awriter_submit(fxh_awriter *aw, struct fxh_writer *w, char **spare, size_t *spare_cap)
+{
+    fxh_awriter_ready(aw, w);              /* the other buffer is free again */
     if (!*spare) { *spare_cap = w->cap; *spare = (char *)malloc(*spare_cap); if (!*spare) err(1, "out of memory"); }
     pthread_mutex_lock(&aw->mu);
     aw->buf = w->buf; aw->len = w->len; aw->state = 1;
@@ -386,15 +395,61 @@ void fxh_awriter_stop(fxh_awriter *aw)
  * LATER submit / wait has returned */
 void fxh_awriter_submit_ext(fxh_awriter *aw, struct fxh_writer *w, const char *buf, size_t len)
 {
-    if (!aw->started) {
-        pthread_mutex_init(&aw->mu, NULL); pthread_cond_init(&aw->cv, NULL);
-        aw->w = w; aw->state = 0; aw->started = 1;
-        if (pthread_create(&aw->th, NULL, fxh_awriter_main, aw) != 0) err(1, "pthread_create");
-    }
-    fxh_awriter_wait(aw);
+    fxh_awriter_ready(aw, w);
     pthread_mutex_lock(&aw->mu);
     aw->buf = buf; aw->len = len; aw->state = 1;
     pthread_cond_broadcast(&aw->cv);
     pthread_mutex_unlock(&aw->mu);
 }
 
+/* ---- a small pool of worker threads: tasks never wait for other tasks ---- */
+static void *fxh_pool_main(void *arg)
+{
+    fxh_pool *P = (fxh_pool *)arg;
+    pthread_mutex_lock(&P->mu);
+    for (;;) {
+        while (P->count == 0 && !P->quit) pthread_cond_wait(&P->cv_work, &P->mu);
+        if (P->count == 0) break;
+        const fxh_task t = P->q[P->head];
+        P->head = (P->head + 1) % P->cap; P->count--;
+        pthread_cond_signal(&P->cv_space);
+        pthread_mutex_unlock(&P->mu);
+        t.fn(t.arg);
+        pthread_mutex_lock(&P->mu);
+    }
+    pthread_mutex_unlock(&P->mu);
+    return NULL;
+}
+
+void fxh_pool_start(fxh_pool *P, int nth, unsigned cap)
+{
+    memset(P, 0, sizeof *P);
+    pthread_mutex_init(&P->mu, NULL); pthread_cond_init(&P->cv_work, NULL); pthread_cond_init(&P->cv_space, NULL);
+    P->cap = cap; P->q = (fxh_task *)calloc(cap, sizeof(fxh_task));
+    if (!P->q) err(1, "out of memory");
+    if (nth > 64) nth = 64;
+    if (nth < 1) nth = 1;
+    P->nth = nth;
+    for (int i = 0; i < nth; ++i) if (pthread_create(&P->th[i], NULL, fxh_pool_main, P) != 0) err(1, "pthread_create");
+}
+
+void fxh_pool_submit(fxh_pool *P, void (*fn)(void *), void *arg)
+{
+    pthread_mutex_lock(&P->mu);
+    while (P->count == P->cap) pthread_cond_wait(&P->cv_space, &P->mu);
+    P->q[(P->head + P->count) % P->cap].fn = fn;
+    P->q[(P->head + P->count) % P->cap].arg = arg;
+    P->count++;
+    pthread_cond_signal(&P->cv_work);
+    pthread_mutex_unlock(&P->mu);
+}
+
+void fxh_pool_stop(fxh_pool *P)       /* queued tasks are still run */
+{
+    pthread_mutex_lock(&P->mu);
+    P->quit = 1;
+    pthread_cond_broadcast(&P->cv_work);
+    pthread_mutex_unlock(&P->mu);
+    for (int i = 0; i < P->nth; ++i) pthread_join(P->th[i], NULL);
+    free(P->q);
+}

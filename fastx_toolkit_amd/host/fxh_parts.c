@@ -46,6 +46,52 @@ off_t fxh_find_cut(int fd, off_t from, off_t size, int lpr, size_t window)
     return (found > 0 && found < size) ? found : -1;
 }
 
+void fxh_totals_add(fxh_totals *tot, const fxh_totals *t)
+{
+    tot->input_sequences += t->input_sequences; tot->input_reads += t->input_reads; tot->output_sequences += t->output_sequences; tot->output_reads += t->output_reads;
+    tot->clip_input += t->clip_input; tot->clip_too_short += t->clip_too_short; tot->clip_adapter_only += t->clip_adapter_only;
+    tot->clip_no_adapter += t->clip_no_adapter; tot->clip_adapter_found += t->clip_adapter_found; tot->clip_n += t->clip_n;
+    tot->masked_reads += t->masked_reads; tot->masked_nucleotides += t->masked_nucleotides; tot->qtrim_dropped += t->qtrim_dropped;
+}
+
+/* ---- the frame both parallel runs of a regular file share (the sharded run below, the one-file run of fxh_strands.c) ----
+ * The attempt runs in a CHILD process.  Irregular input anywhere (or a cut that was no record boundary) abandons it: the reference's behaviour --
+ * message, exit code, what has been written before the bad record -- is defined for ONE stream, so the child empties its output and exits with
+ * FXH_EXIT_ABANDON, and the parent -- which has not touched the GPU -- runs the same input as one stream.  Nothing is ever exec'd or killed with
+ * device work in flight: the child ends like any tool run, after its threads have been joined and its contexts destroyed. */
+/* may this command line be tried at all?  (in_sb: the input file's stat) */
+int fxh_attempt_eligible(const FASTX *fx, const fxg_params *p, struct stat *in_sb)
+{
+    if (fstat(fx->reader->fd, in_sb) != 0 || !S_ISREG(in_sb->st_mode)) return 0;
+    if (strcmp(fx->output_file_name, "-") == 0 || fx->compress_output || g_rename_ids || getenv("FXH_HOST_PARSE")) return 0;
+    if ((p->stages & FXG_STAGE_CLIP) && getenv("FXH_CLIP_SERIAL") != NULL && getenv("FXH_CLIP_PARALLEL") == NULL) return 0;      /* one aligner asked for */
+    if (g_hip_touched) return 0;                 /* this process has used the HIP runtime already (a host that calls in twice): no fork over a live runtime */
+    return 1;
+}
+
+/* 0: this is the child, ready to run the attempt.  1: the child abandoned it -- the caller restores its descriptors and runs one stream.  -1: no child
+ * (errno is fork's).  A child that ended any other way has printed the reports and closed the output: the parent ends as it did, here.
+ * gone_tag: under FXH_TIMING the parent says when `fxh timing <gone_tag>`'s child was gone (NULL: it does not). */
+int fxh_attempt_fork(const char *gone_tag)
+{
+    fflush(NULL);
+    const double t_fork = fxh_now();
+    const pid_t child = fork();
+    if (child < 0) return -1;
+    if (child == 0) {
+        (void)prctl(PR_SET_PDEATHSIG, SIGTERM);  /* a tool process that was killed takes its attempt along */
+        __atomic_store_n(&g_parts_abort, 0, __ATOMIC_RELAXED);
+        g_parts_mode = 1;
+        return 0;
+    }
+    int st = 0;
+    while (waitpid(child, &st, 0) < 0) { if (errno != EINTR) err(1, "waitpid"); }
+    if (gone_tag && getenv("FXH_TIMING")) fprintf(stderr, "fxh timing %s: the child was gone %.3f s after the fork, at %.3f (CLOCK_MONOTONIC)\n", gone_tag, fxh_now() - t_fork, fxh_now());
+    if (WIFEXITED(st) && WEXITSTATUS(st) == FXH_EXIT_ABANDON) return 1;
+    if (WIFSIGNALED(st)) { signal(WTERMSIG(st), SIG_DFL); raise(WTERMSIG(st)); _exit(128 + WTERMSIG(st)); }
+    _exit(WIFEXITED(st) ? WEXITSTATUS(st) : 1);
+}
+
 typedef struct { FASTX *fx; const fxg_params *p; fxh_totals tot; int part, nparts, rc; pthread_t th; off_t start, limit; char name[PATH_MAX + 16]; } fxh_part;
 static void *fxh_part_main(void *arg)
 {
@@ -68,9 +114,7 @@ int fxh_run_parts(FASTX *fx, const fxg_params *p, fxh_totals *tot, int k)
     struct fxh_reader *rd = fx->reader;
     struct stat sb;
     if (k > FXH_MAX_LANES) k = FXH_MAX_LANES;
-    if (rd->fd == STDIN_FILENO || fstat(rd->fd, &sb) != 0 || !S_ISREG(sb.st_mode)) return -1;
-    if (strcmp(fx->output_file_name, "-") == 0 || fx->compress_output || g_rename_ids || getenv("FXH_HOST_PARSE")) return -1;
-    if ((p->stages & FXG_STAGE_CLIP) && getenv("FXH_CLIP_SERIAL") != NULL && getenv("FXH_CLIP_PARALLEL") == NULL) return -1;      /* one aligner asked for */
+    if (rd->fd == STDIN_FILENO || !fxh_attempt_eligible(fx, p, &sb)) return -1;
     const off_t size = sb.st_size, here = lseek(rd->fd, 0, SEEK_CUR);
     const int lpr = fx->read_fastq ? 4 : 2;
     off_t cut[FXH_MAX_LANES + 1];
@@ -79,12 +123,6 @@ int fxh_run_parts(FASTX *fx, const fxg_params *p, fxh_totals *tot, int k)
         cut[r] = fxh_find_cut(rd->fd, (off_t)((unsigned long long)size * (unsigned)r / (unsigned)k), size, lpr, 0);
         if (cut[r] < 0 || cut[r] <= cut[r - 1] || (r == 1 && cut[r] < here)) return -1;       /* small or odd input: one run */
     }
-    /* The sharded attempt runs in a CHILD process.  Irregular input anywhere (or a cut that was no record boundary) abandons it: the
-     * reference's behaviour -- message, exit code, what has been written before the bad record -- is defined for ONE stream, so the
-     * child empties the parts and exits with FXH_EXIT_ABANDON, and this process -- which has not touched the GPU yet -- runs the same
-     * input unsharded (part 0 then receives everything).  Nothing is ever exec'd or killed with device work in flight: the child ends
-     * like any tool run, after its threads have been joined and its contexts destroyed. */
-    if (g_hip_touched) return -1;                /* this process has used the HIP runtime already (a host that calls in twice): no fork over a live runtime */
     /* Every part is opened HERE, before anything has run: an output that cannot take parts -- /dev/null, a FIFO, a directory where the
      * sibling names cannot be created -- means one stream (part 0 alone, as named by the caller), never a failure halfway. */
     int part_fd[FXH_MAX_LANES];
@@ -103,23 +141,16 @@ int fxh_run_parts(FASTX *fx, const fxg_params *p, fxh_totals *tot, int k)
             }
         }
     }
-    fflush(NULL);
-    const pid_t child = fork();
-    if (child < 0) { for (int r = 1; r < k; ++r) close(part_fd[r]); return -1; }
-    if (child > 0) {
-        int st = 0;
-        for (int r = 1; r < k; ++r) close(part_fd[r]);                                  /* the child writes them */
-        while (waitpid(child, &st, 0) < 0) { if (errno != EINTR) err(1, "waitpid"); }
-        if (WIFEXITED(st) && WEXITSTATUS(st) == FXH_EXIT_ABANDON) {
+    const int forked = fxh_attempt_fork(NULL);   /* (the frame above; abandoned: part 0 then receives everything) */
+    if (forked != 0) {
+        for (int r = 1; r < k; ++r) close(part_fd[r]);                                  /* the child wrote them (the wait is the frame's: they stay open here until it is gone) */
+        if (forked > 0) {
             if (lseek(rd->fd, here, SEEK_SET) < 0) err(1, "%s", fx->input_file_name);      /* the child read through the shared descriptor */
             struct fxh_writer *w = fx->writer;
             if (w && w->fd >= 0) { if (ftruncate(w->fd, 0) != 0 || lseek(w->fd, 0, SEEK_SET) < 0) warn("%s", fx->output_file_name); }
-            return -1;
         }
-        if (WIFSIGNALED(st)) { signal(WTERMSIG(st), SIG_DFL); raise(WTERMSIG(st)); _exit(128 + WTERMSIG(st)); }
-        _exit(WIFEXITED(st) ? WEXITSTATUS(st) : 1);                                      /* the child printed the reports and closed the parts */
+        return -1;
     }
-    (void)prctl(PR_SET_PDEATHSIG, SIGTERM);      /* the child: a tool process that was killed takes its sharded attempt along */
     fxh_part *pt = (fxh_part *)calloc((size_t)k, sizeof(fxh_part));
     if (!pt) err(1, "out of memory");
     for (int r = 0; r < k; ++r) {
@@ -134,18 +165,15 @@ int fxh_run_parts(FASTX *fx, const fxg_params *p, fxh_totals *tot, int k)
         f->input_line_number = 0; f->num_input_sequences = f->num_input_reads = f->num_output_sequences = f->num_output_reads = 0;
         pt[r].fx = f;
     }
-    __atomic_store_n(&g_parts_abort, 0, __ATOMIC_RELAXED);
-    g_parts_mode = 1;
     for (int r = 1; r < k; ++r) if (pthread_create(&pt[r].th, NULL, fxh_part_main, &pt[r]) != 0) err(1, "pthread_create");
     fxh_part_main(&pt[0]);
     for (int r = 1; r < k; ++r) pthread_join(pt[r].th, NULL);
     int bad = FXH_ABORTED();
     for (int r = 0; r < k; ++r) if (pt[r].rc != 0) bad = 1;
-    {   /* clipper: every part found reads of one length -- it has to be the SAME length in all of them (a shorter read after a longer one
-         * sees the longer one's tail); otherwise the parent runs the input as one stream, which goes serial where it must */
-        uint32_t len0 = 0;
-        for (int r = 0; r < k && !bad; ++r) { if (!g_part_clip_len[r]) continue; if (!len0) len0 = g_part_clip_len[r]; else if (g_part_clip_len[r] != len0) bad = 1; }
-    }
+    /* clipper: every part found reads of one length -- it has to be the SAME length in all of them; otherwise the parent runs the input as one
+     * stream, which goes serial where it must */
+    uint64_t len0 = 0;
+    for (int r = 0; r < k && !bad; ++r) bad = !fxh_one_length(&len0, g_part_clip_len[r]);
     if (bad) {
         /* Abandoned.  Every thread of every part has been joined and its contexts are gone (fxh_lanes_stop destroys them for a part
          * that stops), the device is idle.  The parts are emptied through their own descriptors, part 0 -- whose descriptor the parent
@@ -168,10 +196,7 @@ int fxh_run_parts(FASTX *fx, const fxg_params *p, fxh_totals *tot, int k)
     }
     for (int r = 0; r < k; ++r) {
         const fxh_totals *t = &pt[r].tot;
-        tot->input_sequences += t->input_sequences; tot->input_reads += t->input_reads; tot->output_sequences += t->output_sequences; tot->output_reads += t->output_reads;
-        tot->clip_input += t->clip_input; tot->clip_too_short += t->clip_too_short; tot->clip_adapter_only += t->clip_adapter_only;
-        tot->clip_no_adapter += t->clip_no_adapter; tot->clip_adapter_found += t->clip_adapter_found; tot->clip_n += t->clip_n;
-        tot->masked_reads += t->masked_reads; tot->masked_nucleotides += t->masked_nucleotides; tot->qtrim_dropped += t->qtrim_dropped;
+        fxh_totals_add(tot, t);
         if (r > 0) fxh_writer_flush(pt[r].fx->writer);
         const off_t out_bytes = r == 0 ? fx->writer->off + (off_t)fx->writer->len : pt[r].fx->writer->off;
         if (ix) fprintf(ix, "%d\t%s\t%lld\t%zu\t%zu\t%lld\n", r, pt[r].name, (long long)(pt[r].limit - pt[r].start), t->input_sequences, t->output_sequences, (long long)out_bytes);

@@ -1,5 +1,6 @@
-/* fxh_priv.h -- shared between the files of the batch path (fxh_batch.c: host-parsed path, run driver; fxh_io.c: block prefetch and writer thread;
- * fxh_lanes.c: the lanes of the device text path; fxh_parts.c: the sharded run).  Not installed. */
+/* fxh_priv.h -- shared between the files of the batch path (fxh_batch.c: host-parsed path, run driver; fxh_io.c: block prefetch, writer thread, pread
+ * loop and task pool; fxh_lanes.c: the lanes of the device text path; fxh_parts.c: the sharded run and the fork frame of an attempt that may be abandoned;
+ * fxh_strands.c: the one-file run -- chunks, strands, sink; fxh_rank.c: its rank-per-GPU job).  Declares only what crosses files.  Not installed. */
 #ifndef FXH_PRIV_H
 #define FXH_PRIV_H
 #define _GNU_SOURCE
@@ -28,6 +29,24 @@ static inline double fxh_now(void)
     struct timespec ts;
     clock_gettime(CLOCK_MONOTONIC, &ts);
     return (double)ts.tv_sec + 1e-9 * (double)ts.tv_nsec;
+}
+
+/* the clipper's one-length rule, a length at a time (the parts', the ranks', the chunks' as they come): every non-zero length equals the first
+ * non-zero one, kept in *len0 (a shorter read after a longer one sees the longer one's tail).  0 = this one does not. */
+static inline int fxh_one_length(uint64_t *len0, uint64_t len)
+{
+    if (len && !*len0) *len0 = len;
+    return !len || len == *len0;
+}
+
+/* a number from the environment: unset or empty = dflt, then clamped to [lo, hi] */
+static inline long fxh_env_long(const char *name, long dflt, long lo, long hi)
+{
+    const char *e = getenv(name);
+    long v = e && *e ? atol(e) : dflt;
+    if (v < lo) v = lo;
+    if (v > hi) v = hi;
+    return v;
 }
 
 typedef struct {
@@ -232,6 +251,20 @@ typedef struct fxh_block {
 
 #define FXH_EXIT_ABANDON 99
 
+/* a small pool of worker threads (fxh_io.c): tasks never wait for other tasks */
+typedef struct { void (*fn)(void *); void *arg; } fxh_task;
+typedef struct fxh_pool {
+    pthread_mutex_t mu;
+    pthread_cond_t cv_work, cv_space;
+    fxh_task *q;
+    unsigned cap, head, count;
+    int quit, nth;
+    pthread_t th[64];
+} fxh_pool;
+
+typedef struct fxh_sink fxh_sink;          /* the sink of the one-file run (fxh_strands.c) */
+typedef struct fxh_rank fxh_rank;          /* what only a rank of a rank-per-GPU job has (fxh_rank.c) */
+
 void fxh_grow_device(fxh_state *st, size_t reads, size_t bytes, int revcomp);
 void fxh_parallel(fxh_job *job, void (*phase)(fxh_worker *));
 void fxh_phase_census(fxh_worker *w);
@@ -252,6 +285,21 @@ void fxh_lane_open_ctx(fxh_lane *ln);
 void fxh_lane_release(fxh_lane *ln);
 int fxh_run_one_file(FASTX *fx, const fxg_params *p, fxh_totals *tot);
 off_t fxh_find_cut(int fd, off_t from, off_t size, int lpr, size_t window);
+size_t fxh_pread_full(int fd, char *dst, size_t n, off_t off);
+void fxh_pool_start(fxh_pool *P, int nth, unsigned cap);
+void fxh_pool_submit(fxh_pool *P, void (*fn)(void *), void *arg);
+void fxh_pool_stop(fxh_pool *P);
+void fxh_totals_add(fxh_totals *tot, const fxh_totals *t);
+int fxh_attempt_eligible(const FASTX *fx, const fxg_params *p, struct stat *in_sb);
+int fxh_attempt_fork(const char *gone_tag);
+int fxh_sink_end(fxh_sink *K, int have_total, uint64_t total);
+void fxh_rendezvous_name(const FASTX *fx, char *dst, size_t cap);
+int fxh_rank_device(int rank, int listed);
+fxh_rank *fxh_rank_open(const FASTX *fx, int rank, int world, int device, int out_fd, uint64_t in_total);
+int fxh_rank_place(fxh_rank *R, fxh_lane *ln, uint64_t off, uint64_t bytes);
+int fxh_rank_finish(fxh_rank *R, const FASTX *fx, fxh_sink *prealloc, fxh_totals *mine, uint64_t local_bytes, int clip_auto, uint64_t clip_len, int bad, uint64_t *job_total);
+void fxh_rank_close(fxh_rank *R);
+void fxh_rank_report(const fxh_rank *R, long long my_start, long long my_end, uint64_t local_bytes);
 void fxh_lanes_stop(fxh_run *R, fxh_lane *lanes, int nlanes, double *t_lane_init);
 void fxh_run_lanes(fxh_run *R, fxh_prefetch *pf, int nlanes, const int *lane_dev, double *t_read, double *t_lane_init);
 int fxh_run_impl(FASTX *fx, const fxg_params *p, fxh_totals *tot, fxh_stats_run *stats, uint64_t **hist_out, uint32_t *cols_out, int part, int nparts);

@@ -667,6 +667,53 @@ def test_one_output_file_attempt_abandoned_on_irregular_input(tools, tmp_path, s
     assert w[0] == 0 and g[0] == 0 and (tmp_path / "t.fq").read_bytes() == (tmp_path / "t_single.fq").read_bytes()
 
 
+def test_both_attempts_abandon_through_one_frame_to_the_one_stream_result(tools, tmp_path):
+    """The one-file run and the sharded run share one frame (fxh_parts.c: fxh_attempt_eligible / fxh_attempt_fork): the attempt lives in a forked child, and an
+    abandoned one leaves the parent to run the input as one stream.  Clean input: the one file and the concatenated parts are the one-stream bytes.  One
+    malformed record in the middle: both attempts say `abandoned`, and both end with the one-stream run's exit code, stderr and partial output.
+    (The child and the parent of an attempt each empty the output through the one descriptor they share, so this test sees a missing truncate only when
+    both of a run's are gone: then the one file keeps the length of its mapping.)"""
+    text = fo.synth_fastq(47, 0, 60000, 100, False)
+    k0 = text.index(b"\n@", len(text) // 2) + 1
+    inp = tmp_path / "in.fq"
+    argv = ["fastq_quality_trim_filter", "-t", "20", "-l", "30", "-q", "20", "-p", "80", "-v"]
+    ways = {"stream": {"FXH_ONE_FILE": "0", "FXH_TIMING": "1"}, "file": _one_file_env("map"), "parts": {"FXH_PARTS": "3", "FXH_STRAND_KB": "512", "FXH_TIMING": "1"}}
+    said = {"file": b"fxh timing one file: abandoned, contexts destroyed, output emptied", "parts": b"fxh timing parts: abandoned, contexts destroyed, parts emptied"}
+
+    def quiet(err):
+        return [l for l in err.splitlines() if not l.startswith(b"fxh timing")]
+
+    for kind, data in (("clean", text), ("bad", text[:k0] + b"#" + text[k0 + 1:])):
+        inp.write_bytes(data)
+        res = {}
+        for way, env in ways.items():
+            out = tmp_path / ("%s_%s.fq" % (kind, way))
+            rc, rep, err = _run([os.path.join(tools, argv[0])] + argv[1:] + ["-i", str(inp), "-o", str(out)], b"", buf_mb="1", extra_env=env)
+            names = [str(out)] + (["%s.%d" % (out, r) for r in (1, 2)] if way == "parts" else [])
+            res[way] = (rc, rep, quiet(err), b"".join(open(f, "rb").read() for f in names))
+            if way != "stream":
+                assert (said[way] in err) == (kind == "bad"), (kind, way, err[-300:])
+            if kind == "clean" and way != "stream":      # the attempt did run: many strands / three parts that all hold text
+                assert b"fxh timing one file (3 strands" in err if way == "file" else all(os.path.getsize(f) > 0 for f in names), (way, err[-300:])
+        assert res["stream"][0] == (0 if kind == "clean" else 1) and 0 < len(res["stream"][3]) < len(text)
+        assert res["file"] == res["stream"] and res["parts"] == res["stream"], (kind, [(w, r[0], r[2], len(r[3])) for w, r in res.items()])
+
+
+def test_every_tally_crosses_the_rank_jobs_counter_block(tools, tmp_path):
+    """A rank job's -v report is rank 0's, made from the job's counter block: a tally of fxh_totals goes into the block and comes back out of the gathered
+    sums (fxh_rank.c: FXH_B_TALLIES).  test_rank_per_gpu_job_* compares the reports of fastx_clipper (the six clip tallies) and of fastq_quality_trim_filter
+    (qtrim_dropped), both with the four record / read counts; the two mask tallies are in no report but the masker's, which is the one compared here."""
+    argv = ["fastq_masker", "-q", "20", "-v"]
+    inp, single, multi = tmp_path / "in.fq", tmp_path / "single", tmp_path / "ranks"
+    inp.write_bytes(fo.synth_fastq(47, 0, 8000, 100, False))
+    want = _run([os.path.join(tools, argv[0])] + argv[1:] + ["-i", str(inp), "-o", str(single)], b"", extra_env={"FXH_ONE_FILE": "0"})
+    res = _rank_job(tools, argv, inp, multi, 2, tmp_path)
+    assert want[0] == 0 and [rc for rc, _, _ in res] == [0, 0], [e[-300:] for _, _, e in res]
+    assert all(b"fxh timing rank %d of 2" % r in res[r][2] for r in range(2))      # the job did run by ranks
+    assert len(want[1].splitlines()) >= 4 and res[0][1].splitlines() == want[1].splitlines() and res[1][1] == b""
+    assert multi.read_bytes() == single.read_bytes()
+
+
 def _rank_job(tools, argv, inp, out, world, tmp_path, extra=None, delays=None):
     """One process per rank, the SAME command line, FXH_RANK / FXH_WORLD in the environment (what mpirun, srun or a shell loop would start)."""
     import emu_py
