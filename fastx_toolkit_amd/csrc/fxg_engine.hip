@@ -472,31 +472,48 @@ extern "C" int fxg_fastq_pack(fxg_ctx *c, const uint8_t *d_text, uint64_t text_l
     return FXG_OK;
 }
 
+extern "C" int fxg_fastq_format_opts(fxg_ctx *c, const uint8_t *d_text, int lines_per_record, const uint32_t *d_line, uint64_t cap_lines, const uint8_t *d_flags,
+                                     uint64_t n, const uint32_t *d_res, uint32_t fwd_start, int reverse, const uint8_t *d_pk_bases, const uint8_t *d_pk_qual,
+                                     const uint64_t *d_pk_off, const uint8_t *d_rows_qual, uint32_t stride, int qoffset, int out_fasta, uint8_t *d_out,
+                                     uint64_t *out_bytes, const fxg_format_opts *opts)
+{
+    if (!c) return FXG_E_INVALID;
+    FXG_TRY(fxg_text_format_opts_check(d_text, lines_per_record, d_line, d_flags, n, d_res, fwd_start, d_pk_bases, d_pk_qual, d_pk_off, d_rows_qual, out_fasta, d_out, out_bytes, opts, c->err, sizeof c->err));
+    if (n == 0) return FXG_OK;
+    FXG_HIP(c, hipSetDevice(c->device));
+    FXG_TRY(fxg_text_reserve(c, (size_t)(n + n / 512 + 4096)));
+    u64 *item = c->text_ws;
+    FxgFormatArgs a = fxg_text_format_args(d_text, d_line, cap_lines, d_flags, item, n, d_res, fwd_start, reverse, d_pk_bases, d_pk_qual, d_pk_off, d_rows_qual, stride, qoffset, out_fasta, d_out);
+    fxg_text_format_args_opts(&a, opts);
+    const u32 nb = (u32)((n + FXG_BLOCK - 1) / FXG_BLOCK);
+    if (lines_per_record == 4) FXG_LAUNCH(c, fxg_kernel_text_sizes<4>, nb, FXG_BLOCK, 0, a, item);
+    else FXG_LAUNCH(c, fxg_kernel_text_sizes<2>, nb, FXG_BLOCK, 0, a, item);
+    FXG_TRY(fxg_scan_u64(c, item, n, item + n));
+    u64 *d_tot = item + n, tot[2] = {0, 0};                    // (the scan is done with its block sums)
+    if (lines_per_record == 4) FXG_LAUNCH(c, fxg_kernel_text_total<4>, 1, 1, 0, a, d_tot);
+    else FXG_LAUNCH(c, fxg_kernel_text_total<2>, 1, 1, 0, a, d_tot);
+    FXG_HIP(c, hipMemcpyAsync(tot, d_tot, sizeof tot, hipMemcpyDeviceToHost, c->stream));
+    if (opts->out_cap != FXG_OUT_CAP_UNCHECKED) {              // nothing may be written before the total is known to fit
+        FXG_HIP(c, hipStreamSynchronize(c->stream));
+        FXG_TRY(fxg_text_format_fits(tot[0], opts->out_cap, c->err, sizeof c->err));
+    }
+    const u32 fgrid = (u32)((n * 16 + FXG_BLOCK - 1) / FXG_BLOCK);
+    if (lines_per_record == 4) FXG_LAUNCH(c, fxg_kernel_text_format<4>, fgrid, FXG_BLOCK, 0, a);
+    else FXG_LAUNCH(c, fxg_kernel_text_format<2>, fgrid, FXG_BLOCK, 0, a);
+    FXG_HIP(c, hipStreamSynchronize(c->stream));
+    *out_bytes = tot[0];
+    return FXG_OK;
+}
+
 extern "C" int fxg_fastq_format(fxg_ctx *c, const uint8_t *d_text, int lines_per_record, const uint32_t *d_line, uint64_t cap_lines, const uint8_t *d_flags,
                                 uint64_t n, const uint32_t *d_res, uint32_t fwd_start, int reverse, const uint8_t *d_pk_bases, const uint8_t *d_pk_qual,
                                 const uint64_t *d_pk_off, const uint8_t *d_rows_qual, uint32_t stride, int qoffset, int out_fasta, uint8_t *d_out,
                                 uint64_t *out_bytes)
 {
-    if (!c) return FXG_E_INVALID;
-    FXG_TRY(fxg_text_format_check(d_text, lines_per_record, d_line, d_flags, n, d_res, d_pk_bases, d_pk_qual, d_pk_off, d_rows_qual, out_fasta, d_out, out_bytes, c->err, sizeof c->err));
-    if (n == 0) return FXG_OK;
-    FXG_HIP(c, hipSetDevice(c->device));
-    FXG_TRY(fxg_text_reserve(c, (size_t)(n + n / 512 + 4096)));
-    u64 *item = c->text_ws;
-    const FxgFormatArgs a = fxg_text_format_args(d_text, d_line, cap_lines, d_flags, item, n, d_res, fwd_start, reverse, d_pk_bases, d_pk_qual, d_pk_off, d_rows_qual, stride, qoffset, out_fasta, d_out);
-    const u32 nb = (u32)((n + FXG_BLOCK - 1) / FXG_BLOCK);
-    if (lines_per_record == 4) FXG_LAUNCH(c, fxg_kernel_text_sizes<4>, nb, FXG_BLOCK, 0, a, item);
-    else FXG_LAUNCH(c, fxg_kernel_text_sizes<2>, nb, FXG_BLOCK, 0, a, item);
-    u64 last_item = 0, last_scan = 0;
-    FXG_HIP(c, hipMemcpyAsync(&last_item, item + (n - 1), sizeof(u64), hipMemcpyDeviceToHost, c->stream));
-    FXG_TRY(fxg_scan_u64(c, item, n, item + n));
-    FXG_HIP(c, hipMemcpyAsync(&last_scan, item + (n - 1), sizeof(u64), hipMemcpyDeviceToHost, c->stream));
-    const u32 fgrid = (u32)((n * 16 + FXG_BLOCK - 1) / FXG_BLOCK);
-    if (lines_per_record == 4) FXG_LAUNCH(c, fxg_kernel_text_format<4>, fgrid, FXG_BLOCK, 0, a);
-    else FXG_LAUNCH(c, fxg_kernel_text_format<2>, fgrid, FXG_BLOCK, 0, a);
-    FXG_HIP(c, hipStreamSynchronize(c->stream));
-    *out_bytes = fxg_text_out_bytes(last_scan, last_item);
-    return FXG_OK;
+    const fxg_format_opts plain = fxg_text_format_opts_plain();
+    if (!d_res) return FXG_E_INVALID;
+    return fxg_fastq_format_opts(c, d_text, lines_per_record, d_line, cap_lines, d_flags, n, d_res, fwd_start, reverse, d_pk_bases, d_pk_qual, d_pk_off, d_rows_qual, stride, qoffset, out_fasta,
+                                 d_out, out_bytes, &plain);
 }
 
 extern "C" int fxg_fasta_weights(fxg_ctx *c, const uint8_t *d_text, const uint32_t *d_line, uint64_t cap_lines, uint64_t n, const uint32_t *d_res,

@@ -430,6 +430,10 @@ struct FxgFormatArgs {
     int qoffset;
     u32 out_fasta;                    // write FASTA whatever the input was (fastq_to_fasta)
     uint8_t *out;
+    // output modes (fxg_format_opts); all zero = the input's own names and quality encoding
+    const uint16_t *len;              // res == null: every record is kept whole, its length from the index
+    u32 id_mode, id_both, qual_mode;
+    u64 ordinal_base;
 };
 
 FXG_HD u32 fxg_num_width(int v) { return (v < 0 ? 1u : 0u) + ((v <= -10 || v >= 10) ? 2u : 1u); }     // -15..93
@@ -450,21 +454,47 @@ FXG_HD u64 fxg_text_rank(const u64 *item_scan, u64 r)
     return rank + (((item_scan[r] >> FXG_FMT_OFF_BITS) - rank) & FXG_FMT_RANK_MASK);
 }
 
+// D(first, first + count): the decimal digits of the integers first .. first + count - 1 together (first + count - 1 <= 2^64 - 1).  Ordinal ids
+// are sized with it: a record's name is as wide as its rank says, and the rank comes out of the same scan as the offset, so the scan runs
+// over zero-width ids and the digits of the count ids before a record are added in closed form, one term per width.
+FXG_HD u64 fxg_dec_width_sum(u64 first, u64 count)
+{
+    if (!count) return 0;
+    const u64 last = first + count - 1ull;
+    u64 sum = 0, lo = 0, p = 10;                             // width w: lo .. p - 1 (0 is one digit wide)
+    for (u32 w = 1; w <= 20u; ++w) {
+        const u64 hi = w == 20u ? ~0ull : p - 1ull;
+        const u64 x = first > lo ? first : lo, y = last < hi ? last : hi;
+        if (x <= y) sum += (u64)w * (y - x + 1ull);
+        lo = p; p *= 10ull;                                  // (10^20 wraps: w = 20 does not read it)
+    }
+    return sum;
+}
+FXG_HD u32 fxg_dec_width(u64 v) { u32 w = 1; for (u64 p = 10; w < 20u && v >= p; p *= 10ull) ++w; return w; }
+
+// the res word of record r: the pipeline's, or "kept whole" at its indexed length when the block went through no stage
+FXG_HD u32 fxg_fmt_res(const FxgFormatArgs &a, u64 r) { return a.res ? a.res[r] : (0x10000u | (u32)a.len[r]); }
+// whether record r's quality line goes out as numbers
+FXG_HD bool fxg_fmt_numeric(const FxgFormatArgs &a, u64 r) { return a.qual_mode == FXG_QUAL_NUMERIC || (a.qual_mode == FXG_QUAL_AS_INPUT && (a.flags[r] & FXG_REC_NUMERIC)); }
+// copies of the id in a record whose id is rewritten: the '@' line, and the '+' line of FASTQ output with id_both
+FXG_HD u32 fxg_fmt_id_copies(const FxgFormatArgs &a, bool fastq) { return fastq && a.id_both ? 2u : 1u; }
+
+// Ordinal ids (FXG_ID_ORDINAL) are sized zero bytes wide here: fxg_text_format_record and fxg_text_total add their digits from the rank.
 template <int LPR>
 FXG_HD u64 fxg_text_size_record(const FxgFormatArgs &a, u64 r)
 {
-    const u32 w = a.res[r];
+    const u32 w = fxg_fmt_res(a, r);
     u64 v = 0;
     if ((w >> 16) & 1u) {
         const u64 b = (u64)LPR * r;
-        const u32 name_len = a.le[b] - a.ls[b] - 1u;                                // without the prefix character
         const u32 len = w & 0xFFFFu;
+        const u32 name_len = a.id_mode == FXG_ID_INPUT ? a.le[b] - a.ls[b] - 1u : (a.id_mode == FXG_ID_SEQUENCE ? len : 0u);     // without the prefix character
         u64 bytes = (u64)name_len + len + 3u;                                       // prefix, name, LF, bases, LF
         if (LPR == 4 && !a.out_fasta) {
             const u32 l2 = a.le[b + 2] - a.ls[b + 2];
-            const u32 name2_len = l2 ? l2 - 1u : 0u;                                // first byte dropped (R5)
+            const u32 name2_len = (a.id_mode != FXG_ID_INPUT && a.id_both) ? name_len : (l2 ? l2 - 1u : 0u);     // first byte dropped (R5)
             u32 qbytes = len;
-            if (a.flags[r] & FXG_REC_NUMERIC) {                                     // "%d" joined by blanks: only the digit counts depend on the values
+            if (fxg_fmt_numeric(a, r)) {                                            // "%d" joined by blanks: only the digit counts depend on the values
                 const u32 rl = a.le[b + 1] - a.ls[b + 1];
                 const u32 q0 = a.rev ? rl - a.fwd_start - len : (a.pk_bases ? 0u : a.fwd_start);
                 const uint8_t *q = a.rows_qual + r * (u64)a.stride + q0;
@@ -476,6 +506,17 @@ FXG_HD u64 fxg_text_size_record(const FxgFormatArgs &a, u64 r)
         v = bytes | (1ull << FXG_FMT_OFF_BITS);
     }
     return v;
+}
+
+// bytes and kept records of the whole block, from the scanned items: the last record's scanned item plus its own, and the digits of the ordinal ids
+template <int LPR>
+FXG_HD void fxg_text_total(const FxgFormatArgs &a, u64 *tot)
+{
+    const u64 r = a.n - 1, item = fxg_text_size_record<LPR>(a, r);
+    const u64 kept = fxg_text_rank(a.item_scan, r) + (item >> FXG_FMT_OFF_BITS);
+    u64 bytes = (a.item_scan[r] + item) & FXG_FMT_OFF_MASK;
+    if (a.id_mode == FXG_ID_ORDINAL) bytes += fxg_fmt_id_copies(a, LPR == 4 && !a.out_fasta) * fxg_dec_width_sum(a.ordinal_base + 1ull, kept);
+    tot[0] = bytes; tot[1] = kept;
 }
 
 // n bytes from src to dst, both arbitrarily aligned, by `lanes` cooperating lanes (lane id `l`); add is applied per byte
@@ -492,50 +533,96 @@ FXG_HD void fxg_copy_bytes(uint8_t *dst, const uint8_t *src, u32 n, u32 l, u32 l
     for (u32 i = (full << 4) + l; i < n; i += lanes) dst[i] = (uint8_t)((int)src[i] + add);
 }
 
+// "%d" of the Phred+33 code c at p; returns the bytes written (fxg_num_width)
+FXG_HD u32 fxg_put_num(uint8_t *p, uint8_t c)
+{
+    int v = (int)c - 33;
+    u32 k = 0;
+    if (v < 0) { p[k++] = '-'; v = -v; }
+    if (v >= 10) p[k++] = (uint8_t)('0' + v / 10);
+    p[k++] = (uint8_t)('0' + v % 10);
+    return k;
+}
+
+// A numeric quality line -- len values joined by blanks, then LF, as write_ascii's numeric form does (fastx.c:421-438) -- by the 16 lanes of a
+// record's group.  Lane l takes the values [l * share, (l + 1) * share) and sums their widths (each value but the line's first brings its blank
+// along); an exclusive scan over the group's 16 lanes turns the sums into offsets; every lane writes its share there, the last lane the LF.
+// The scan is four __shfl_up steps of width 16: no LDS, no barrier.  All 16 lanes of a group must arrive here together: the caller's branches
+// around this call depend on the record alone (r, its res word and flags, the modes), never on the lane.  The serial form (the host pass, which
+// is what tests/emu runs lane after lane) adds up the widths before its share itself.
+FXG_HD void fxg_text_write_numeric(uint8_t *qd, const uint8_t *src, u32 len, u32 l)
+{
+    const u32 share = (len + 15u) >> 4;
+    const u32 i0 = l * share < len ? l * share : len, i1 = i0 + share < len ? i0 + share : len;
+    u32 mine = 0;
+    for (u32 i = i0; i < i1; ++i) mine += fxg_num_width((int)src[i] - 33) + (i ? 1u : 0u);
+#if defined(__HIP_DEVICE_COMPILE__)
+    u32 incl = mine;
+#pragma unroll
+    for (int d = 1; d < 16; d <<= 1) { const u32 t = __shfl_up(incl, d, 16); if ((int)l >= d) incl += t; }
+    u32 k = incl - mine;
+#else
+    u32 k = 0;
+    for (u32 i = 0; i < i0; ++i) k += fxg_num_width((int)src[i] - 33) + (i ? 1u : 0u);
+#endif
+    for (u32 i = i0; i < i1; ++i) {
+        if (i) qd[k++] = ' ';
+        k += fxg_put_num(qd + k, src[i]);
+    }
+    if (l == 15u) qd[k] = '\n';
+}
+
 // 16 lanes format one kept record: "@name\nSEQ\n+name2\nQUAL\n" (FASTQ) or ">name\nSEQ\n" (FASTA).
 // Forward outputs are slices of the input lines; reverse-complemented / masked outputs come from the engine's packed arrays at
-// pk_off[rank] and hold Phred+33 codes.  Numeric quality lines are printed from the codes by one lane.
+// pk_off[rank] and hold Phred+33 codes.  Numeric quality lines are printed from the codes (fxg_text_write_numeric).
+// Output modes: the id is the input's name, the record's 1-based rank from ordinal_base on (one lane writes its <= 20 digits), or the
+// OUTPUT bases (copied from where the bases line comes from); id_both puts it on the '+' line too.  A quality line goes out as it came in,
+// or forced to characters / numbers: characters of a record that came in as numbers are its row's codes + (Q - 33).
 template <int LPR>
 FXG_HD void fxg_text_format_record(const FxgFormatArgs &a, u64 r, u32 l)
 {
-    const u32 w = a.res[r];
+    const u32 w = fxg_fmt_res(a, r);
     if (!((w >> 16) & 1u)) return;
     const u64 sc = a.item_scan[r];
-    const u64 off = sc & FXG_FMT_OFF_MASK;
+    u64 off = sc & FXG_FMT_OFF_MASK;
     const u64 b = (u64)LPR * r;
     const u32 o0 = a.ls[b], o1 = a.ls[b + 1];
-    const u32 name_len = a.le[b] - o0 - 1u;
     const u32 len = w & 0xFFFFu;
     const bool fastq = (LPR == 4 && !a.out_fasta);
+    const u64 rank = (a.pk_bases || a.id_mode == FXG_ID_ORDINAL) ? fxg_text_rank(a.item_scan, r) : 0ull;
+    const u64 po = a.pk_bases ? a.pk_off[rank] : 0ull;
+    const uint8_t *bsrc = a.pk_bases ? a.pk_bases + po : a.text + o1 + a.fwd_start;
+    u32 name_len = a.le[b] - o0 - 1u;
+    const uint8_t *nsrc = a.text + o0 + 1;
+    u64 id = 0;
+    if (a.id_mode == FXG_ID_ORDINAL) {
+        off += fxg_fmt_id_copies(a, fastq) * fxg_dec_width_sum(a.ordinal_base + 1ull, rank);
+        id = a.ordinal_base + rank + 1ull;
+        name_len = fxg_dec_width(id);
+    } else if (a.id_mode == FXG_ID_SEQUENCE) { name_len = len; nsrc = bsrc; }
     uint8_t *d = a.out + off;
-    const u64 po = a.pk_bases ? a.pk_off[fxg_text_rank(a.item_scan, r)] : 0ull;
     if (l == 0) { d[0] = fastq ? '@' : '>'; d[1 + name_len] = '\n'; d[2 + name_len + len] = '\n'; }
-    fxg_copy_bytes(d + 1, a.text + o0 + 1, name_len, l, 16, 0);
-    if (a.pk_bases) fxg_copy_bytes(d + 2 + name_len, a.pk_bases + po, len, l, 16, 0);
-    else fxg_copy_bytes(d + 2 + name_len, a.text + o1 + a.fwd_start, len, l, 16, 0);
+    if (a.id_mode != FXG_ID_ORDINAL) fxg_copy_bytes(d + 1, nsrc, name_len, l, 16, 0);
+    else if (l == 1u) { u64 v = id; for (u32 k = name_len; k-- > 0u; v /= 10ull) d[1 + k] = (uint8_t)('0' + v % 10ull); }
+    fxg_copy_bytes(d + 2 + name_len, bsrc, len, l, 16, 0);
     if (!fastq) return;
     const u32 o2 = a.ls[b + 2], o3 = a.ls[b + 3];
-    const u32 l2 = a.le[b + 2] - o2, name2_len = l2 ? l2 - 1u : 0u;
+    const u32 l2 = a.le[b + 2] - o2;
+    const bool id2 = a.id_mode != FXG_ID_INPUT && a.id_both;
+    const u32 name2_len = id2 ? name_len : (l2 ? l2 - 1u : 0u);
     uint8_t *q = d + 3 + name_len + len;                 // '+'
     if (l == 0) { q[0] = '+'; q[1 + name2_len] = '\n'; }
-    fxg_copy_bytes(q + 1, a.text + o2 + 1, name2_len, l, 16, 0);
+    if (!id2) fxg_copy_bytes(q + 1, a.text + o2 + 1, name2_len, l, 16, 0);
+    else if (a.id_mode == FXG_ID_SEQUENCE) fxg_copy_bytes(q + 1, bsrc, len, l, 16, 0);
+    else if (l == 2u) { u64 v = id; for (u32 k = name_len; k-- > 0u; v /= 10ull) q[1 + k] = (uint8_t)('0' + v % 10ull); }
     uint8_t *qd = q + 2 + name2_len;
-    if (!(a.flags[r] & FXG_REC_NUMERIC)) {
+    const bool was_numeric = (a.flags[r] & FXG_REC_NUMERIC) != 0;
+    if (!fxg_fmt_numeric(a, r)) {
         if (a.pk_bases) fxg_copy_bytes(qd, a.pk_qual + po, len, l, 16, a.qoffset - 33);
+        else if (was_numeric) fxg_copy_bytes(qd, a.rows_qual + r * (u64)a.stride + a.fwd_start, len, l, 16, a.qoffset - 33);
         else fxg_copy_bytes(qd, a.text + o3 + a.fwd_start, len, l, 16, 0);    // R8: q + Q is the input byte
         if (l == 0) qd[len] = '\n';
-    } else if (l == 0) {                                  // numbers separated by blanks, as write_ascii / numeric output does (fastx.c:421-438)
-        const uint8_t *src = a.pk_bases ? a.pk_qual + po : a.rows_qual + r * (u64)a.stride + a.fwd_start;
-        u32 k = 0;
-        for (u32 i = 0; i < len; ++i) {
-            int v = (int)src[i] - 33;
-            if (i) qd[k++] = ' ';
-            if (v < 0) { qd[k++] = '-'; v = -v; }
-            if (v >= 10) qd[k++] = (uint8_t)('0' + v / 10);
-            qd[k++] = (uint8_t)('0' + v % 10);
-        }
-        qd[k] = '\n';
-    }
+    } else fxg_text_write_numeric(qd, a.pk_bases ? a.pk_qual + po : a.rows_qual + r * (u64)a.stride + a.fwd_start, len, l);
 }
 
 #ifndef FXG_HOST_EMULATION
@@ -545,6 +632,10 @@ __global__ __launch_bounds__(FXG_BLOCK) void fxg_kernel_text_sizes(const FxgForm
     const u64 r = (u64)blockIdx.x * FXG_BLOCK + threadIdx.x;
     if (r < a.n) item[r] = fxg_text_size_record<LPR>(a, r);
 }
+
+// one thread, after the scan: {bytes, kept records} of the block, which the host needs before the format kernel may write
+template <int LPR>
+__global__ void fxg_kernel_text_total(const FxgFormatArgs a, u64 *tot) { fxg_text_total<LPR>(a, tot); }
 
 template <int LPR>
 __global__ __launch_bounds__(FXG_BLOCK) void fxg_kernel_text_format(const FxgFormatArgs a)
@@ -587,15 +678,35 @@ static inline int fxg_text_pack_check(const uint8_t *text, int lpr, const u32 *l
     if (lpr == 2 && qual) FXG_PLAN_FAIL("FASTA records have no qualities");
     return FXG_OK;
 }
-static inline int fxg_text_format_check(const uint8_t *text, int lpr, const u32 *line, const uint8_t *flags, u64 n, const u32 *res, const uint8_t *pk_bases, const uint8_t *pk_qual,
-                                        const uint64_t *pk_off, const uint8_t *rows_qual, int out_fasta, const uint8_t *out, uint64_t *out_bytes, char *err, size_t cap)
+// fxg_fastq_format_opts: everything refused before a kernel runs.  o->out_cap is checked by fxg_text_format_fits once the scan has the total.
+static inline int fxg_text_format_opts_check(const uint8_t *text, int lpr, const u32 *line, const uint8_t *flags, u64 n, const u32 *res, u32 fwd_start, const uint8_t *pk_bases, const uint8_t *pk_qual,
+                                             const uint64_t *pk_off, const uint8_t *rows_qual, int out_fasta, const uint8_t *out, uint64_t *out_bytes, const fxg_format_opts *o, char *err, size_t cap)
 {
-    if (!text || !line || !flags || !res || !out || !out_bytes || !fxg_text_lpr_ok(lpr)) return FXG_E_INVALID;
+    if (!text || !line || !flags || !o || (!res && !o->d_len) || !out || !out_bytes || !fxg_text_lpr_ok(lpr)) return FXG_E_INVALID;
     *out_bytes = 0;
+    if (o->id_mode > FXG_ID_SEQUENCE) FXG_PLAN_FAIL("unknown id mode %u", o->id_mode);
+    if (o->qual_mode > FXG_QUAL_NUMERIC) FXG_PLAN_FAIL("unknown quality mode %u", o->qual_mode);
+    if (!res && (pk_bases || fwd_start)) FXG_PLAN_FAIL("without res every record is kept whole: no packed output and no first base");
+    if (o->id_mode == FXG_ID_ORDINAL && o->ordinal_base > ~0ull - n) FXG_PLAN_FAIL("ordinal ids from %llu on pass 2^64 - 1", (unsigned long long)o->ordinal_base + 1ull);
     if (n == 0) return FXG_OK;
     const bool fastq_out = lpr == 4 && !out_fasta;
     if (pk_bases && (!pk_off || (fastq_out && !pk_qual))) FXG_PLAN_FAIL("packed output needs bases, out_off and (FASTQ) qual");
     if (fastq_out && !rows_qual) FXG_PLAN_FAIL("FASTQ output needs the batch's quality rows (numeric records are printed from them)");
+    return FXG_OK;
+}
+// fxg_fastq_format: the input's names and encodings, and a capacity the caller vouches for (FXG_OUT_CAP_UNCHECKED)
+static inline fxg_format_opts fxg_text_format_opts_plain(void) { fxg_format_opts o = {}; o.out_cap = FXG_OUT_CAP_UNCHECKED; return o; }
+static inline int fxg_text_format_check(const uint8_t *text, int lpr, const u32 *line, const uint8_t *flags, u64 n, const u32 *res, const uint8_t *pk_bases, const uint8_t *pk_qual,
+                                        const uint64_t *pk_off, const uint8_t *rows_qual, int out_fasta, const uint8_t *out, uint64_t *out_bytes, char *err, size_t cap)
+{
+    const fxg_format_opts o = fxg_text_format_opts_plain();
+    if (!res) return FXG_E_INVALID;
+    return fxg_text_format_opts_check(text, lpr, line, flags, n, res, 0u, pk_bases, pk_qual, pk_off, rows_qual, out_fasta, out, out_bytes, &o, err, cap);
+}
+// after the scan, before the format kernel: the block's bytes against what d_out can take
+static inline int fxg_text_format_fits(u64 total, u64 out_cap, char *err, size_t cap)
+{
+    if (total > out_cap) FXG_PLAN_FAIL("the formatted block needs %llu bytes, d_out takes %llu", (unsigned long long)total, (unsigned long long)out_cap);
     return FXG_OK;
 }
 // the arguments of the two format kernels over an item array of n words (and the scan's levels behind them)
@@ -606,7 +717,12 @@ static inline FxgFormatArgs fxg_text_format_args(const uint8_t *text, const u32 
     a.text = text; a.ls = line; a.le = line + cap_lines; a.res = res; a.flags = flags; a.item_scan = item; a.n = n;
     a.fwd_start = fwd_start; a.rev = reverse ? 1u : 0u; a.pk_bases = pk_bases; a.pk_qual = pk_qual; a.pk_off = (const u64 *)pk_off;
     a.rows_qual = rows_qual; a.stride = stride; a.qoffset = qoffset; a.out_fasta = out_fasta ? 1u : 0u; a.out = out;
+    a.len = nullptr; a.id_mode = FXG_ID_INPUT; a.id_both = 0u; a.qual_mode = FXG_QUAL_AS_INPUT; a.ordinal_base = 0ull;
     return a;
+}
+static inline void fxg_text_format_args_opts(FxgFormatArgs *a, const fxg_format_opts *o)
+{
+    a->len = o->d_len; a->id_mode = o->id_mode; a->id_both = o->id_both ? 1u : 0u; a->qual_mode = o->qual_mode; a->ordinal_base = o->ordinal_base;
 }
 // bytes written: the last record's scanned item (the offset in the low bits) plus its own
 static inline u64 fxg_text_out_bytes(u64 last_scan, u64 last_item) { return (last_scan + last_item) & FXG_FMT_OFF_MASK; }

@@ -24,7 +24,7 @@ EXPORTS = [
     "fxg_memcpy_d2h", "fxg_memset_device", "fxg_timer_start", "fxg_timer_stop", "fxg_run_pipeline",
     "fxg_run_qtrim_qfilter", "fxg_run_clip", "fxg_run_revcomp_trim", "fxg_read_counters", "fxg_scan_recoveries", "fxg_synth_generate",
     "fxg_last_launch_info", "fxg_set_profiling", "fxg_last_kernel_ms", "fxg_profiled_kernel_ms", "fxg_set_clip_history", "fxg_run_quality_stats",
-    "fxg_fastq_index", "fxg_fastq_pack", "fxg_fastq_format", "fxg_fasta_weights", "fxg_host_register", "fxg_host_unregister",
+    "fxg_fastq_index", "fxg_fastq_pack", "fxg_fastq_format", "fxg_fastq_format_opts", "fxg_fasta_weights", "fxg_host_register", "fxg_host_unregister",
     "fxg_shard_range", "fxg_epilogue", "fxg_concat_pwrite", "fxg_concat_peer", "fxg_device_count", "fxg_device_numa_node", "fxg_comm_create", "fxg_comm_destroy", "fxg_epilogue_rccl",
     "fxg_barcode_prepare", "fxg_barcode_split",
 ]
@@ -51,6 +51,22 @@ class FxgTextInfo(C.Structure):
     _fields_ = [("lines", C.c_uint64), ("records", C.c_uint64), ("consumed", C.c_uint64), ("max_len", C.c_uint32),
                 ("min_len", C.c_uint32), ("irregular", C.c_uint32), ("first_bad", C.c_uint32), ("numeric_records", C.c_uint32),
                 ("has_cr", C.c_uint32)]
+
+
+ID_INPUT, ID_ORDINAL, ID_SEQUENCE = 0, 1, 2          # fxg_format_opts.id_mode
+QUAL_AS_INPUT, QUAL_ASCII, QUAL_NUMERIC = 0, 1, 2    # fxg_format_opts.qual_mode
+
+
+class FxgFormatOpts(C.Structure):
+    _fields_ = [("id_mode", C.c_uint32), ("id_both", C.c_uint32), ("ordinal_base", C.c_uint64), ("qual_mode", C.c_uint32),
+                ("out_cap", C.c_uint64), ("d_len", C.c_void_p)]
+
+
+def format_bound(text_len, n, id_mode=ID_INPUT, qual_mode=QUAL_AS_INPUT):
+    """Bytes a formatted block can come to: fxg_fastq_format's text_len + n + 16, 40 more per record for ordinal ids on two lines, twice the
+    text more for sequence ids on two lines, and four bytes per quality value ("-15 ") for numeric lines."""
+    cap = (4 * text_len if qual_mode == QUAL_NUMERIC else text_len) + n + 16
+    return cap + (40 * n if id_mode == ID_ORDINAL else 2 * text_len if id_mode == ID_SEQUENCE else 0)
 
 
 MAX_BARCODE = 64               # FXG_MAX_BARCODE
@@ -137,6 +153,7 @@ def load_library(path=None):
     L.fxg_fastq_index.argtypes = [vp, vp, u64, i32, i32, vp, u64, vp, vp, C.POINTER(FxgTextInfo)]
     L.fxg_fastq_pack.argtypes = [vp, vp, u64, i32, vp, u64, vp, u64, u32, i32, vp, vp, C.POINTER(u32)]
     L.fxg_fastq_format.argtypes = [vp, vp, i32, vp, u64, vp, u64, vp, u32, i32, vp, vp, vp, vp, u32, i32, i32, vp, C.POINTER(u64)]
+    L.fxg_fastq_format_opts.argtypes = L.fxg_fastq_format.argtypes + [C.POINTER(FxgFormatOpts)]
     L.fxg_fasta_weights.argtypes = [vp, vp, vp, u64, u64, vp, C.POINTER(u64 * 8)]
     L.fxg_host_register.argtypes = [vp, vp, C.c_size_t]
     L.fxg_host_unregister.argtypes = [vp, vp]
@@ -446,14 +463,24 @@ class Engine:
                                             qoffset, bases.data_ptr(), qual.data_ptr() if want_qual else None, C.byref(irr)))
         return bases[:n * stride].view(n, stride), (qual[:n * stride].view(n, stride) if want_qual else None), irr.value
 
-    def fastq_format(self, d_text, text_len, ix, n, res, fwd_start=0, packed=None, reverse=False, rows_qual=None, qoffset=33, out_fasta=False):
-        out = self.torch.empty(text_len + n + 16, dtype=self.torch.uint8, device=self.device)
-        nb = C.c_uint64()
+    def fastq_format(self, d_text, text_len, ix, n, res=None, fwd_start=0, packed=None, reverse=False, rows_qual=None, qoffset=33, out_fasta=False,
+                     id_mode=ID_INPUT, id_both=False, ordinal_base=0, qual_mode=QUAL_AS_INPUT, lens=None):
+        """Format the kept records of an indexed block.  res=None (with lens from fastq_index): a block that went through no stage, every
+        record whole.  id_mode / id_both / ordinal_base / qual_mode: fxg_format_opts (include/fxg.h); the output is sized for the modes here."""
         pb, pq, po = (packed[0].data_ptr(), packed[1].data_ptr() if packed[1] is not None else None, packed[2].data_ptr()) if packed else (None, None, None)
+        plain = res is not None and (id_mode, bool(id_both), qual_mode) == (ID_INPUT, False, QUAL_AS_INPUT)
+        cap = format_bound(text_len, n, id_mode, qual_mode)
+        out = self.torch.empty(cap, dtype=self.torch.uint8, device=self.device)
+        nb = C.c_uint64()
+        args = (self.ctx, d_text.data_ptr(), ix.lpr, ix.line.data_ptr(), ix.cap_lines, ix.flags.data_ptr(), n, res.data_ptr() if res is not None else None,
+                fwd_start, int(reverse), pb, pq, po, rows_qual.data_ptr() if rows_qual is not None else None,
+                rows_qual.shape[1] if rows_qual is not None else 0, qoffset, int(out_fasta), out.data_ptr(), C.byref(nb))
         self._after_torch()
-        self._check(self.lib.fxg_fastq_format(self.ctx, d_text.data_ptr(), ix.lpr, ix.line.data_ptr(), ix.cap_lines, ix.flags.data_ptr(), n, res.data_ptr(),
-                                              fwd_start, int(reverse), pb, pq, po, rows_qual.data_ptr() if rows_qual is not None else None,
-                                              rows_qual.shape[1] if rows_qual is not None else 0, qoffset, int(out_fasta), out.data_ptr(), C.byref(nb)))
+        if plain:
+            self._check(self.lib.fxg_fastq_format(*args))
+        else:
+            o = FxgFormatOpts(id_mode, int(bool(id_both)), ordinal_base, qual_mode, cap, lens.data_ptr() if lens is not None else None)
+            self._check(self.lib.fxg_fastq_format_opts(*args, C.byref(o)))
         return out[:nb.value]
 
     def fasta_weights(self, d_text, ix, n, res):

@@ -1,6 +1,6 @@
 /* fxh_batch.c -- see fxh_batch.h: buffers and record output, the host-parsed path, the run driver and the public entry points. */
 #include "fxh_priv.h"
-int g_rename_ids = 0;
+fxh_format g_fmt;
 
 void fxh_default_params(fxg_params *p, int qoffset)
 {
@@ -59,7 +59,9 @@ static void fxh_grow(fxh_state *st, size_t reads, size_t bytes, int revcomp)
     fxh_grow_device(st, reads, bytes, revcomp);
 }
 
-void fxh_set_rename_ids(int on) { g_rename_ids = on; }
+void fxh_set_rename_ids(int on) { fxh_set_output_ids(on ? FXG_ID_ORDINAL : FXG_ID_INPUT, 0, 0); }
+void fxh_set_output_ids(uint32_t id_mode, int id_both, int count32) { g_fmt.id_mode = id_mode; g_fmt.id_both = id_both ? 1u : 0u; g_fmt.count32 = count32; }
+int fxh_format_opts_available(void) { return fxg_fastq_format_opts != NULL; }
 
 /* Size (dst == NULL) or write one kept record; seq/qual point at `len` output bytes; qual bytes are either raw input
  * characters (raw_qual) or Phred+33 codes (engine output / numeric input).  Returns the number of bytes. */
@@ -69,20 +71,25 @@ static size_t fxh_emit(const FASTX *fx, const fxh_rec *r, const uint8_t *seq, co
     size_t k = 0;
 #define PUTC(ch) do { if (d) d[k] = (char)(ch); k++; } while (0)
 #define PUTS(ptr, n_) do { if (d) memcpy(d + k, (ptr), (n_)); k += (n_); } while (0)
-    PUTC(fx->output_sequence_id_prefix);
-    if (g_rename_ids) {                      /* the record's 1-based position in the output replaces its name */
-        char num[24];
-        int nd = 0;
-        size_t v = out_index;
+    char num[24];
+    int nd = 0;
+    if (g_fmt.id_mode == FXG_ID_ORDINAL) {   /* the record's 1-based position in the output replaces its name (the renamer's counter is an unsigned int) */
+        size_t v = g_fmt.count32 ? (size_t)(unsigned int)out_index : out_index;
         do { num[nd++] = (char)('0' + v % 10); v /= 10; } while (v);
-        while (nd) { --nd; PUTC(num[nd]); }      /* no side effects inside PUTC's argument: it is not evaluated when sizing */
-    } else PUTS(r->name, r->name_len);
+    }
+#define PUTID() do { \
+        if (g_fmt.id_mode == FXG_ID_ORDINAL) { for (int j = nd; j > 0; --j) PUTC(num[j - 1]); } \
+        else PUTS(seq, len);                 /* FXG_ID_SEQUENCE: the output bases */ \
+    } while (0)
+    PUTC(fx->output_sequence_id_prefix);
+    if (g_fmt.id_mode != FXG_ID_INPUT) PUTID(); else PUTS(r->name, r->name_len);
     PUTC('\n');
     PUTS(seq, len); PUTC('\n');
     if (fx->write_fastq) {
         const int ascii = fx->copy_input_fastq_format_to_output ? r->is_ascii : fx->write_fastq_ascii;   /* R6 */
         PUTC('+');
-        PUTS(r->name2, r->name2_len); PUTC('\n');
+        if (g_fmt.id_mode != FXG_ID_INPUT && g_fmt.id_both) PUTID(); else PUTS(r->name2, r->name2_len);
+        PUTC('\n');
         if (ascii) {
             if (raw_qual) PUTS(qual, len);                                              /* R8: q + Q is the input byte */
             else { const int sh = fx->fastq_ascii_quality_offset - 33; for (size_t i = 0; i < len; ++i) PUTC(qual[i] + sh); }
@@ -97,6 +104,7 @@ static size_t fxh_emit(const FASTX *fx, const fxh_rec *r, const uint8_t *seq, co
         }
         PUTC('\n');
     }
+#undef PUTID
 #undef PUTC
 #undef PUTS
     return k;
@@ -448,6 +456,12 @@ static int fxh_host_engine(fxh_run *R, fxh_hb *hb)
         fx->num_input_sequences = tot->input_sequences; fx->num_input_reads = tot->input_reads;
         return 0;
     }
+    if (!p->stages) {                          /* a tool without a stage (renamer, converter): every record is kept whole; the rows were only the validation */
+        memset(ctr, 0, FXG_NCOUNTERS * sizeof *ctr);
+        ctr[FXG_C_INPUT] = ctr[FXG_C_KEPT] = n;
+        for (size_t i = 0; i < n; ++i) st->h_res[i] = (1u << 16) | st->h_len[i];
+        return 1;
+    }
     fxg_out out = {st->d_res, job->revcomp ? st->d_out_bases : NULL, (job->revcomp && job->has_q) ? st->d_out_qual : NULL, NULL, NULL, NULL, st->d_counters};
     fxg_params pp = *p;
     pp.qoffset = 33;                        /* rows hold Phred+33 codes whatever -Q was */
@@ -599,7 +613,7 @@ int fxh_run_impl(FASTX *fx, const fxg_params *p, fxh_totals *tot, fxh_stats_run 
     char *rd_spare = NULL;
     R.overlap = getenv("FXH_NO_OVERLAP") == NULL;
     /* device-side parse/format (FASTQ or FASTA in; the same, or FASTA, out); FXH_HOST_PARSE=1 forces the host parser */
-    const int gpu_text = !stats && !g_rename_ids && getenv("FXH_HOST_PARSE") == NULL;
+    const int gpu_text = !stats && ((fxh_format_plain(&g_fmt) && p->stages) || fxh_format_opts_available()) && getenv("FXH_HOST_PARSE") == NULL;
     int nlanes = 0;
     int lane_dev[FXH_MAX_LANES];
     if (gpu_text) {
@@ -668,6 +682,7 @@ int fxh_run_impl(FASTX *fx, const fxg_params *p, fxh_totals *tot, fxh_stats_run 
 
 int fxh_run_tool(FASTX *fx, const fxg_params *p, fxh_totals *tot)
 {
+    g_fmt.qual_mode = !fx->write_fastq || fx->copy_input_fastq_format_to_output ? FXG_QUAL_AS_INPUT : fx->write_fastq_ascii ? FXG_QUAL_ASCII : FXG_QUAL_NUMERIC;
     const char *pe = getenv("FXH_PARTS");
     int k = pe ? atoi(pe) : fxh_auto_parts(fx);
     if (k > FXH_MAX_LANES) k = FXH_MAX_LANES;

@@ -47,6 +47,15 @@ int fxh_run_quality_stats(FASTX *fx, uint64_t **hist, uint32_t *cols, fxh_totals
 /* fastq_to_fasta -r: kept records are renamed to their 1-based output index (fastq_to_fasta.c:83-84).  Set before fxh_run_tool. */
 void fxh_set_rename_ids(int on);
 
+/* Ids and '+' lines of the records a run writes (include/fxg.h: fxg_format_opts).  id_mode: FXG_ID_INPUT, FXG_ID_ORDINAL (the record's 1-based
+ * position in the output) or FXG_ID_SEQUENCE (its output bases); id_both: the '+' line of FASTQ output carries the id too (fastx_renamer.c:93,97);
+ * count32: ordinals are counted as the renamer does, in an unsigned int (they go on modulo 2^32).  The quality encoding is the writer's
+ * (OUTPUT_FASTQ_ASCII_QUAL / OUTPUT_FASTQ_NUMERIC_QUAL / as the input).  Set before fxh_run_tool. */
+void fxh_set_output_ids(uint32_t id_mode, int id_both, int count32);
+/* Whether the loaded engine library formats such records on the device.  Where it does not, fastq_to_fasta -r runs through the host parser (as before
+ * the device formatter had modes) and a tool without a stage runs its records through fastx_read_next_record / fastx_write_record. */
+int fxh_format_opts_available(void);
+
 /* fxg_params with the reference tools' defaults (qoffset from -Q). */
 void fxh_default_params(fxg_params *p, int qoffset);
 

@@ -40,7 +40,8 @@ void fxh_lane_run(fxh_lane *ln)
         st->d_text_cap = len + len / 8 + 4096;
         FXG_CHECK(st, fxg_malloc_device(st->ctx, st->d_text_cap, (void **)&st->d_text));
         /* the output can be longer than the input: an empty third line still gets its '+' (fastx.c:460), one byte per record */
-        FXG_CHECK(st, fxg_malloc_device(st->ctx, st->d_text_cap + st->d_text_cap / 7 + 64, (void **)&st->d_out_text));
+        st->d_out_text_cap = st->d_text_cap + st->d_text_cap / 7 + 64;
+        FXG_CHECK(st, fxg_malloc_device(st->ctx, st->d_out_text_cap, (void **)&st->d_out_text));
     }
     const int lpr = ln->lpr;
     const size_t cap_lines = len * 4 / 7 + 16;              /* the shortest records, "@\nA\n\nI\n" and ">\nA\n", have 1.75 / 2 bytes per line */
@@ -77,6 +78,14 @@ void fxh_lane_run(fxh_lane *ln)
     ln->fixed_len = info.min_len == info.max_len ? info.max_len : 0u;
     if (ln->clip_guard && !ln->fixed_len) return;           /* ragged block of a clipper run: the one-aligner mode takes over at this block (fxh_clip_go_serial) */
     if ((uint64_t)n * stride > (uint64_t)8 * len + (1u << 20)) return;   /* ragged beyond reason: the host path handles it */
+    const fxh_format *fmt = &g_fmt;
+    const int plain = fxh_format_plain(fmt);
+    if (!plain && st->d_out_text_cap < fxh_format_bound(fmt, len, n)) {      /* rewritten ids and numeric quality lines outgrow the input */
+        fxg_free_device(st->ctx, st->d_out_text);
+        st->d_out_text = NULL;
+        st->d_out_text_cap = (size_t)fxh_format_bound(fmt, st->d_text_cap, n + n / 8);
+        FXG_CHECK(st, fxg_malloc_device(st->ctx, st->d_out_text_cap, (void **)&st->d_out_text));
+    }
     fxh_grow_device(st, n, (size_t)n * stride + 16, revcomp);
     uint32_t irr = 0;
     FXG_CHECK(st, fxg_fastq_pack(st->ctx, st->d_text, len, lpr, st->d_ls, st->d_ls_cap, st->d_flags, n, stride, ln->qoffset, st->d_bases,
@@ -89,24 +98,63 @@ void fxh_lane_run(fxh_lane *ln)
         FXG_CHECK(st, fxg_malloc_device(st->ctx, st->d_off_cap * sizeof(uint64_t), (void **)&st->d_out_off));
     }
     const int fixed = info.min_len == info.max_len;
-    fxg_batch in = {st->d_bases, ln->has_q ? st->d_qual : NULL, fixed ? NULL : st->d_len16, info.max_len, stride, n};
-    fxg_out out = {st->d_res, revcomp ? st->d_out_bases : NULL, (revcomp && ln->has_q) ? st->d_out_qual : NULL, NULL, NULL, revcomp ? st->d_out_off : NULL, st->d_counters};
-    fxg_params pp = *ln->p;
-    pp.qoffset = 33;
-    FXG_CHECK(st, fxg_run_pipeline(st->ctx, &in, &pp, &out));
-    FXH_TCALL(3);
-    {
+    const uint32_t *d_res = st->d_res;
+    if (ln->p->stages) {
+        fxg_batch in = {st->d_bases, ln->has_q ? st->d_qual : NULL, fixed ? NULL : st->d_len16, info.max_len, stride, n};
+        fxg_out out = {st->d_res, revcomp ? st->d_out_bases : NULL, (revcomp && ln->has_q) ? st->d_out_qual : NULL, NULL, NULL, revcomp ? st->d_out_off : NULL, st->d_counters};
+        fxg_params pp = *ln->p;
+        pp.qoffset = 33;
+        FXG_CHECK(st, fxg_run_pipeline(st->ctx, &in, &pp, &out));
+        FXH_TCALL(3);
         int rc = fxg_read_counters(st->ctx, st->d_counters, ln->ctr);
         if (rc == FXG_E_DEVICE && (ln->ctr[FXG_C_ERRORS] & FXG_DEV_ERR_BAD_BASE)) return;   /* the host parser prints the reference's message at its turn */
         if (rc != 0) errx(1, "GPU engine error %d: %s", rc, fxg_last_error(st->ctx));
+        FXH_TCALL(4);
+        fxh_note_recoveries(st);
+    } else {                                    /* a tool without a stage: index and pack were the validation (and gave the rows a converter prints from); every record is kept whole */
+        memset(ln->ctr, 0, sizeof ln->ctr);
+        ln->ctr[FXG_C_INPUT] = ln->ctr[FXG_C_KEPT] = n;
+        d_res = NULL;
+        if (lpr == 2) {                         /* the read-count tallies of FASTA ids want a res[]: made here from the indexed lengths */
+            uint16_t *l16 = (uint16_t *)malloc(n * (sizeof(uint16_t) + sizeof(uint32_t)) + sizeof(uint32_t));      /* lengths, then (on a 4-byte boundary) res */
+            if (!l16) err(1, "out of memory");
+            uint32_t *res = (uint32_t *)(l16 + n + (n & 1u));
+            FXG_CHECK(st, fxg_memcpy_d2h(st->ctx, l16, st->d_len16, n * sizeof(uint16_t)));
+            FXG_CHECK(st, fxg_sync(st->ctx));
+            for (uint64_t i = 0; i < n; ++i) res[i] = (1u << 16) | l16[i];
+            FXG_CHECK(st, fxg_memcpy_h2d(st->ctx, st->d_res, res, n * sizeof(uint32_t)));
+            FXG_CHECK(st, fxg_sync(st->ctx));
+            free(l16);
+            d_res = st->d_res;
+        }
     }
-    FXH_TCALL(4);
-    fxh_note_recoveries(st);
-    if (lpr == 2) FXG_CHECK(st, fxg_fasta_weights(st->ctx, st->d_text, st->d_ls, st->d_ls_cap, n, st->d_res, ln->weighted));
+    if (lpr == 2) FXG_CHECK(st, fxg_fasta_weights(st->ctx, st->d_text, st->d_ls, st->d_ls_cap, n, d_res, ln->weighted));
     uint64_t out_bytes = 0;
-    FXG_CHECK(st, fxg_fastq_format(st->ctx, st->d_text, lpr, st->d_ls, st->d_ls_cap, st->d_flags, n, st->d_res, ln->fwd_start, ln->reverse,
-                                   revcomp ? st->d_out_bases : NULL, (revcomp && ln->has_q) ? st->d_out_qual : NULL, revcomp ? st->d_out_off : NULL,
-                                   ln->has_q ? st->d_qual : NULL, stride, ln->qoffset, ln->out_fasta, st->d_out_text, &out_bytes));
+    if (plain && d_res) {
+        FXG_CHECK(st, fxg_fastq_format(st->ctx, st->d_text, lpr, st->d_ls, st->d_ls_cap, st->d_flags, n, d_res, ln->fwd_start, ln->reverse,
+                                       revcomp ? st->d_out_bases : NULL, (revcomp && ln->has_q) ? st->d_out_qual : NULL, revcomp ? st->d_out_off : NULL,
+                                       ln->has_q ? st->d_qual : NULL, stride, ln->qoffset, ln->out_fasta, st->d_out_text, &out_bytes));
+    } else {
+        fxg_format_opts fo = {fmt->id_mode, fmt->id_both, 0, fmt->qual_mode, st->d_out_text_cap, st->d_len16};
+        if (fmt->id_mode == FXG_ID_ORDINAL && ln->ord) {      /* this block's first id: the count of the blocks before it -- the one thing a lane waits for another for */
+            fxh_ord *o = ln->ord;
+            const uint64_t kept = ln->ctr[FXG_C_KEPT];
+            pthread_mutex_lock(&o->mu);
+            while (o->next != ln->seq && !o->stop) pthread_cond_wait(&o->cv, &o->mu);
+            const int go = !o->stop && fxh_ord_on_device(o->base, kept, fmt->count32);
+            if (go) {                           /* base and kept are both known: the next block's lane need not wait for this one's format */
+                fo.ordinal_base = o->base;
+                o->base = fxh_ord_next_base(o->base, kept, fmt->count32);
+                o->next = ln->seq + 1;
+                pthread_cond_broadcast(&o->cv);
+            }
+            pthread_mutex_unlock(&o->mu);
+            if (!go) return;                    /* the run is ending, or the renamer's 32-bit counter wraps inside this block: the host parser's (it publishes the count at the block's turn) */
+        }
+        FXG_CHECK(st, fxg_fastq_format_opts(st->ctx, st->d_text, lpr, st->d_ls, st->d_ls_cap, st->d_flags, n, d_res, ln->fwd_start, ln->reverse,
+                                            revcomp ? st->d_out_bases : NULL, (revcomp && ln->has_q) ? st->d_out_qual : NULL, revcomp ? st->d_out_off : NULL,
+                                            ln->has_q ? st->d_qual : NULL, stride, ln->qoffset, ln->out_fasta, st->d_out_text, &out_bytes, &fo));
+    }
     FXH_TCALL(5);
     if (ln->on_size) ln->on_size(ln, out_bytes);           /* the block's place in ONE output file depends only on the sizes before it: known here, before the download */
     if (ln->on_place) {                                     /* rank mode of the one-file run: the text stays on the device for now */
@@ -195,11 +243,11 @@ static void *fxh_lane_main(void *arg)
     return NULL;
 }
 
-static void fxh_lane_post(fxh_lane *ln, char *base, size_t cap, const char *text, size_t len, uint64_t records, int slot)
+static void fxh_lane_post(fxh_lane *ln, char *base, size_t cap, const char *text, size_t len, uint64_t records, int slot, uint64_t seq)
 {
     pthread_mutex_lock(&ln->mu);
     ln->text_base = base; ln->text_cap = cap;
-    ln->text = text; ln->len = len; ln->records = records; ln->slot = slot; ln->state = 1;
+    ln->text = text; ln->len = len; ln->records = records; ln->slot = slot; ln->seq = seq; ln->state = 1;
     pthread_cond_broadcast(&ln->cv);
     pthread_mutex_unlock(&ln->mu);
 }
@@ -335,8 +383,10 @@ static fxh_lane *fxh_lanes_start(fxh_run *R, int nlanes, const int *lane_dev)
     pthread_mutex_init(&pinned->mu, NULL);
     fxh_lane *lanes = (fxh_lane *)calloc((size_t)nlanes, sizeof(fxh_lane));
     if (!lanes) err(1, "out of memory");
+    pthread_mutex_init(&R->ord.mu, NULL); pthread_cond_init(&R->ord.cv, NULL);
     for (int i = 0; i < nlanes; ++i) {
         fxh_lane *ln = &lanes[i];
+        if (g_fmt.id_mode == FXG_ID_ORDINAL) ln->ord = &R->ord;
         ln->id = i; ln->device = lane_dev[i]; ln->p = R->p; ln->revcomp = R->job.revcomp; ln->fwd_start = R->job.fwd_start;
         ln->qoffset = fx->fastq_ascii_quality_offset;
         ln->reverse = (R->p->stages & FXG_STAGE_REVCOMP) != 0; ln->lpr = R->job.lpr; ln->has_q = R->job.has_q; ln->out_fasta = !fx->write_fastq;
@@ -411,6 +461,13 @@ static int fxh_lanes_emit(fxh_run *R, fxh_lane *lanes, fxh_block *b)
         *rd = save;
         fx->input_line_number = save_line;
         R->at_eof = 0;
+        if (g_fmt.id_mode == FXG_ID_ORDINAL) {      /* the host parser numbered the block's records from the run's count; the next block's lane takes it from here */
+            pthread_mutex_lock(&R->ord.mu);
+            R->ord.base = fxh_ord_next_base(R->tot->output_sequences, 0, g_fmt.count32);
+            R->ord.next = b->seq + 1;
+            pthread_cond_broadcast(&R->ord.cv);
+            pthread_mutex_unlock(&R->ord.mu);
+        }
     }
     fx->num_input_sequences = R->tot->input_sequences; fx->num_input_reads = R->tot->input_reads;
     fx->num_output_sequences = R->tot->output_sequences; fx->num_output_reads = R->tot->output_reads;
@@ -455,6 +512,10 @@ static void fxh_cut_records(fxh_run *R, size_t fresh_nl, int have_carry, unsigne
 void fxh_lanes_stop(fxh_run *R, fxh_lane *lanes, int nlanes, double *t_lane_init)
 {
     /* (when an error is pending, blocks after the bad record are abandoned, like everything after an errx() in the reference) */
+    pthread_mutex_lock(&R->ord.mu);      /* a lane waiting for the count of a block that will never be emitted comes back without its block */
+    R->ord.stop = 1;
+    pthread_cond_broadcast(&R->ord.cv);
+    pthread_mutex_unlock(&R->ord.mu);
     for (int i = 0; i < nlanes; ++i) {
         fxh_lane *ln = &lanes[i];
         pthread_mutex_lock(&ln->mu);
@@ -495,7 +556,7 @@ static void fxh_clip_go_serial(fxh_run *R, fxh_lane *lanes, int nlanes, fxh_bloc
     l0->clip_history = 1;
     R->clip_auto = 0; R->st_shared = 1;
     if (R->clip_seed_len) {                 /* (no record before the block: the aligner is fresh, as at the start of a serial run) */
-        fxh_lane_post(l0, NULL, 0, R->clip_seed, R->clip_seed_len, 1, (int)(lane_uses[0]++ & 1u));
+        fxh_lane_post(l0, NULL, 0, R->clip_seed, R->clip_seed_len, 1, (int)(lane_uses[0]++ & 1u), 0);
         fxh_lane_wait(l0);
         if (!l0->handled) errx(1, "internal error: the record before the first ragged block did not pass the device path a second time");
     }
@@ -528,7 +589,7 @@ void fxh_run_lanes(fxh_run *R, fxh_prefetch *pf, int nlanes, const int *lane_dev
         while (next_emit < nblocks && (nblocks - next_emit >= (size_t)nl || input_done)) {
             fxh_block *eb = &blk[next_emit % (size_t)NB];
             if (eb->lane >= 0 && !eb->posted) {          /* a block fxh_clip_go_serial took back: lane 0 runs it now, with history */
-                fxh_lane_post(&lanes[0], eb->buf, rd->cap + 1, eb->buf + eb->beg, eb->end - eb->beg, eb->records, (int)(lane_uses[0]++ & 1u));
+                fxh_lane_post(&lanes[0], eb->buf, rd->cap + 1, eb->buf + eb->beg, eb->end - eb->beg, eb->records, (int)(lane_uses[0]++ & 1u), eb->seq);
                 eb->posted = 1;
             }
             const int erc = fxh_lanes_emit(R, lanes, eb);
@@ -560,7 +621,7 @@ void fxh_run_lanes(fxh_run *R, fxh_prefetch *pf, int nlanes, const int *lane_dev
         const uint64_t records = lines / lpr;
         R->t_index += fxh_now() - t0;
         fxh_block *b = &blk[nblocks % (size_t)NB];
-        b->buf = rd->buf; b->beg = rd->beg; b->line0 = fx->input_line_number; b->records = records; b->lane = -1; b->posted = 0;
+        b->buf = rd->buf; b->beg = rd->beg; b->line0 = fx->input_line_number; b->records = records; b->lane = -1; b->posted = 0; b->seq = nblocks;
         if (rd->eof && (lines % lpr != 0 || records == 0)) {
             /* ragged end of input: the host parser owns the message; hand it everything that is left */
             b->end = end; b->eof = 1;
@@ -571,7 +632,7 @@ void fxh_run_lanes(fxh_run *R, fxh_prefetch *pf, int nlanes, const int *lane_dev
             b->end = cut; b->eof = (rd->eof && cut == end);
             const int li = (int)(nblocks % (size_t)nl);
             b->lane = li; b->posted = 1;
-            fxh_lane_post(&lanes[li], rd->buf, rd->cap + 1, rd->buf + rd->beg, cut - rd->beg, records, (int)(lane_uses[li]++ & 1u));
+            fxh_lane_post(&lanes[li], rd->buf, rd->cap + 1, rd->buf + rd->beg, cut - rd->beg, records, (int)(lane_uses[li]++ & 1u), b->seq);
             rd->beg = cut < rd->end ? cut : rd->end;
             carry_lines = lines - (unsigned long long)lpr * records - (end > rd->end ? 1u : 0u); have_carry = 1;   /* complete lines left in the unread tail */
             fx->input_line_number += (unsigned long long)lpr * records;

@@ -63,7 +63,8 @@ void fxh_totals_add(fxh_totals *tot, const fxh_totals *t)
 int fxh_attempt_eligible(const FASTX *fx, const fxg_params *p, struct stat *in_sb)
 {
     if (fstat(fx->reader->fd, in_sb) != 0 || !S_ISREG(in_sb->st_mode)) return 0;
-    if (strcmp(fx->output_file_name, "-") == 0 || fx->compress_output || g_rename_ids || getenv("FXH_HOST_PARSE")) return 0;
+    if (strcmp(fx->output_file_name, "-") == 0 || fx->compress_output || g_fmt.id_mode == FXG_ID_ORDINAL || getenv("FXH_HOST_PARSE")) return 0;      /* (ordinal ids count across the whole output: one stream) */
+    if (!(fxh_format_plain(&g_fmt) && p->stages) && !fxh_format_opts_available()) return 0;
     if ((p->stages & FXG_STAGE_CLIP) && getenv("FXH_CLIP_SERIAL") != NULL && getenv("FXH_CLIP_PARALLEL") == NULL) return 0;      /* one aligner asked for */
     if (g_hip_touched) return 0;                 /* this process has used the HIP runtime already (a host that calls in twice): no fork over a live runtime */
     return 1;

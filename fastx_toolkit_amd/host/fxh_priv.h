@@ -75,7 +75,7 @@ typedef struct {
     uint32_t *d_ls;                        /* line starts [d_ls_cap] then line ends [d_ls_cap] */
     uint16_t *d_len16;
     uint64_t *d_out_off;
-    size_t d_text_cap, d_ls_cap, d_off_cap;
+    size_t d_text_cap, d_ls_cap, d_off_cap, d_out_text_cap;
     const void *registered[4];
     int recoveries_seen;                   /* fxg_scan_recoveries at the last look (fxh_note_recoveries) */
 } fxh_state;
@@ -162,7 +162,35 @@ extern int g_parts_abort;                  /* sharded run: some part met input i
 extern pthread_mutex_t g_first_ctx_mu;     /* the HIP runtime's first-use initialisation: one thread at a time */
 extern int g_hip_touched;                  /* this process has initialised the HIP runtime (a context, or the device query of fxh_bind_near_device): never fork() after that */
 extern int g_parts_mode;                   /* a sharded run is under way (fxh_run_parts) */
-extern int g_rename_ids;
+/* what the formatter of a run writes in place of the input's ids and quality encoding (fxh_set_output_ids; qual_mode is the writer's, fxh_run_tool) */
+typedef struct fxh_format { uint32_t id_mode, id_both, qual_mode; int count32; } fxh_format;
+extern fxh_format g_fmt;
+static inline int fxh_format_plain(const fxh_format *f) { return f->id_mode == FXG_ID_INPUT && f->qual_mode == FXG_QUAL_AS_INPUT; }
+/* the entry the modes need; a library without it (an older libfxg.so, the CPU tier's look-alike) leaves the reference null */
+extern int fxg_fastq_format_opts(fxg_ctx *, const uint8_t *, int, const uint32_t *, uint64_t, const uint8_t *, uint64_t, const uint32_t *, uint32_t, int, const uint8_t *, const uint8_t *,
+                                 const uint64_t *, const uint8_t *, uint32_t, int, int, uint8_t *, uint64_t *, const fxg_format_opts *) __attribute__((weak));
+/* bytes the formatted text of `text` bytes in `records` records can come to: an empty third line gets its '+' (one byte per record), ordinal ids
+ * are at most 20 digits on two lines, sequence ids the bases on two lines, a numeric quality value at most four bytes ("-15 ") */
+static inline uint64_t fxh_format_bound(const fxh_format *f, uint64_t text, uint64_t records)
+{
+    uint64_t b = (f->qual_mode == FXG_QUAL_NUMERIC ? 4 * text : text) + records + 64;
+    if (f->id_mode == FXG_ID_ORDINAL) b += 40 * records;
+    if (f->id_mode == FXG_ID_SEQUENCE) b += 2 * text;
+    return b;
+}
+/* the same for a whole output file made from `in` bytes of input, as the one-file forms reserve it: the input's own ids and encoding give at most 8/7 of the input */
+static inline uint64_t fxh_format_file_bound(const fxh_format *f, uint64_t in)
+{
+    return (fxh_format_plain(f) ? in + in / 7 : fxh_format_bound(f, in, in / 4)) + (1u << 20);
+}
+/* Ordinal ids over lanes.  Block k's first id is base + 1, base = the records written by the blocks before it: whoever knows block k's count
+ * -- its lane, as soon as the counters are in, or the main thread once the host parser has put the block through -- publishes base + kept for
+ * block k + 1.  Only a lane's format + download waits for it. */
+typedef struct fxh_ord { pthread_mutex_t mu; pthread_cond_t cv; uint64_t next, base; int stop; } fxh_ord;
+/* The renamer counts in an unsigned int (fastx_renamer.c:47, "%u"); the device counts in 64 bits.  A block whose ids base + 1 .. base + kept all
+ * fit the counter is the device's; the block in which it would pass 2^32 - 1 goes through the host parser, which wraps as the reference does. */
+static inline int fxh_ord_on_device(uint64_t base, uint64_t kept, int count32) { return !count32 || base + kept <= 0xFFFFFFFFull; }
+static inline uint64_t fxh_ord_next_base(uint64_t base, uint64_t kept, int count32) { return count32 ? (base + kept) & 0xFFFFFFFFull : base + kept; }
 extern uint32_t g_part_clip_len[FXH_MAX_LANES];      /* clipper parts: the one read length each part saw (0: not a clipper run / no reads) */
 struct fxh_pinned { pthread_mutex_t mu; const void *ptr[FXH_MAX_LANES + 4]; int n; };
 
@@ -183,6 +211,7 @@ typedef struct fxh_lane {
     uint32_t fwd_start;
     const char *text; size_t len;          /* job: whole records, every line '\n'-terminated */
     uint64_t records;
+    fxh_ord *ord; uint64_t seq;            /* run with ordinal ids: the chain of the blocks' counts, and this job's place in it */
     int clip_history;                      /* this lane is the one aligner of a fastx_clipper run */
     int clip_guard;                        /* clipper run in its parallel phase (fxh_run.clip_auto): a block whose reads are not all of one length is handed back untouched */
     uint32_t fixed_len;                    /* result: the one length of the block's reads, 0 = they differ (or the block was not indexed) */
@@ -230,6 +259,7 @@ typedef struct fxh_run {
     int part, nparts;                      /* sharded run (FXH_PARTS): this run is part `part` of `nparts`; irregular input aborts it (fxh_run_parts) */
     int aborted;
     struct fxh_pinned pinned;              /* input buffers the lanes have page-locked */
+    fxh_ord ord;                           /* (used when the run writes ordinal ids) */
     unsigned long n_fallback;
     double t_index, t_pack, t_gpu, t_fmt, t_init;
     double t_wait_lane, t_wait_writer, t_drain;      /* lanes loop: main thread blocked on a lane / on the writer / final drain */
@@ -245,6 +275,7 @@ typedef struct fxh_block {
     int eof;                               /* the input ends with this block */
     unsigned long long line0;              /* lines read before it */
     uint64_t records;
+    uint64_t seq;                          /* its number in the run */
     int lane;                              /* -1: not given to a lane (ragged end of input, oversized record): host parser */
     int posted;                            /* its lane has the job (0 only between fxh_clip_go_serial and the block's turn) */
 } fxh_block;

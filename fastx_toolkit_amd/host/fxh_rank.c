@@ -127,7 +127,7 @@ fxh_rank *fxh_rank_open(const FASTX *fx, int rank, int world, int device, int ou
     R->lane.device = device;
     fxh_lane_open_ctx(&R->lane);
     R->ctx = R->lane.st.ctx;
-    R->arena_cap = in_total + in_total / 7 + (1u << 20);
+    R->arena_cap = fxh_format_file_bound(&g_fmt, in_total);
     if (fxg_malloc_device(R->ctx, (size_t)R->arena_cap, (void **)&R->arena) != 0 || !R->arena)
         errx(1, "rank %d of %d: %.1f GB of device memory for this rank's share of the output are not to be had (%s); start more ranks", rank, world,
              1e-9 * (double)R->arena_cap, fxg_last_error(R->ctx));

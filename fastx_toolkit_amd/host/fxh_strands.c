@@ -270,7 +270,7 @@ static void fxh_sink_open(fxh_sink *K, pthread_mutex_t *mu, pthread_cond_t *cv, 
         want_map = 0;
         if (rank == 0) {
             K->alloc_in_total = job_in_total;
-            K->map_len = (job_in_total + job_in_total / 7 + (1u << 20) + 4095u) & ~(uint64_t)4095u;
+            K->map_len = (fxh_format_file_bound(&g_fmt, job_in_total) + 4095u) & ~(uint64_t)4095u;
             if (fallocate(w0->fd, 0, 0, 4096) == 0) {
                 K->prealloc = 1; K->alloc_end = 4096;
                 pthread_rwlock_init(&K->gate, NULL);
@@ -279,7 +279,7 @@ static void fxh_sink_open(fxh_sink *K, pthread_mutex_t *mu, pthread_cond_t *cv, 
         }
     }
     if (want_map) {
-        K->map_len = (in_total + in_total / 7 + (1u << 20) + 4095u) & ~(uint64_t)4095u;      /* an empty third line still gets its '+': at most 8/7 of the input */
+        K->map_len = (fxh_format_file_bound(&g_fmt, in_total) + 4095u) & ~(uint64_t)4095u;      /* an empty third line still gets its '+': at most 8/7 of the input */
         void *m = MAP_FAILED;
         if (ftruncate(w0->fd, (off_t)K->map_len) == 0) m = mmap(NULL, (size_t)K->map_len, PROT_READ | PROT_WRITE, MAP_SHARED, w0->fd, 0);
         if (m != MAP_FAILED && fallocate(w0->fd, 0, 0, 4096) == 0) {

@@ -85,6 +85,18 @@ static int fxh_when_holds(const fxh_report_line *l)
     return 0;
 }
 
+int fxh_tool_record_loop(FASTX *fx, fxh_totals *tot, void (*edit)(FASTX *fx))
+{
+    memset(tot, 0, sizeof *tot);
+    while (fastx_read_next_record(fx)) {
+        if (edit) edit(fx);
+        fastx_write_record(fx);
+    }
+    tot->input_sequences = num_input_sequences(fx); tot->input_reads = num_input_reads(fx);
+    tot->output_sequences = num_output_sequences(fx); tot->output_reads = num_output_reads(fx);
+    return 1;
+}
+
 int fxh_tool_main(const fxh_tool *tool, int argc, char *argv[])
 {
     static FASTX fastx;

@@ -70,5 +70,9 @@ typedef struct fxh_tool {
     int (*alt_run)(const long *v, FASTX *fx, const fxg_params *p, fxh_totals *tot);      /* optional: a mode of the tool that is not an engine run (1 = it ran) */
 } fxh_tool;
 
+/* alt_run of a tool without a stage where the engine library has no formatter modes: the reference's own loop over the record API, with `edit`
+ * (may be NULL) between fastx_read_next_record and fastx_write_record.  Returns 1. */
+int fxh_tool_record_loop(FASTX *fx, fxh_totals *tot, void (*edit)(FASTX *fx));
+
 int fxh_tool_main(const fxh_tool *tool, int argc, char *argv[]);
 #endif

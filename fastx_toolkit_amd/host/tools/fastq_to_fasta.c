@@ -22,7 +22,7 @@ static void configure(const long *v, const char *s, fxg_params *p)
     (void)s;
     p->stages = FXG_STAGE_NFILTER;
     p->nf_keep_n = v[KEEP_N] ? 1u : 0u;
-    fxh_set_rename_ids((int)v[RENAME]);           /* kept records are renamed to their 1-based output index (fastq_to_fasta.c:83-84) */
+    fxh_set_output_ids(v[RENAME] ? FXG_ID_ORDINAL : FXG_ID_INPUT, 0, 0);      /* kept records are renamed to their 1-based output index, a size_t (fastq_to_fasta.c:83-84) */
 }
 static const fxh_tool tool = {
     "usage: fastq_to_fasta [-h] [-r] [-n] [-v] [-z] [-i INFILE] [-o OUTFILE]\n"

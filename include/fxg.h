@@ -36,7 +36,7 @@
 extern "C" {
 #endif
 
-#define FXG_ABI_VERSION 4
+#define FXG_ABI_VERSION 5
 
 /* ---- error codes ---- */
 #define FXG_OK            0
@@ -281,6 +281,29 @@ int  fxg_fastq_format(fxg_ctx *ctx, const uint8_t *d_text, int lines_per_record,
                       uint64_t records, const uint32_t *d_res, uint32_t fwd_start, int reverse, const uint8_t *d_pk_bases, const uint8_t *d_pk_qual,
                       const uint64_t *d_pk_off, const uint8_t *d_rows_qual, uint32_t stride, int qoffset, int out_fasta, uint8_t *d_out,
                       uint64_t *out_bytes);
+/* fxg_fastq_format with output modes: the ids and the quality encoding of the records written (fastq_to_fasta -r, fastx_renamer,
+ * fastq_quality_converter).  All modes zero: exactly fxg_fastq_format.  d_res may be NULL when opts->d_len is given: a block that went through
+ * no stage, every record kept whole (then no packed arrays and fwd_start 0).  The block's size is known before anything is written: more than
+ * opts->out_cap bytes is refused (FXG_E_INVALID, fxg_last_error says how many) with d_out untouched; unknown mode values are refused too. */
+#define FXG_ID_INPUT     0u   /* the input's own name lines */
+#define FXG_ID_ORDINAL   1u   /* the record's running number (fastq_to_fasta.c -r, fastx_renamer.c -n COUNT) */
+#define FXG_ID_SEQUENCE  2u   /* the record's OUTPUT bases (fastx_renamer.c -n SEQ) */
+#define FXG_QUAL_AS_INPUT 0u  /* every record in the encoding it came in */
+#define FXG_QUAL_ASCII    1u  /* characters, code + Q (fastx.c:406-419) */
+#define FXG_QUAL_NUMERIC  2u  /* numbers joined by blanks (fastx.c:421-438) */
+#define FXG_OUT_CAP_UNCHECKED (~0ull)   /* out_cap: the caller vouches for d_out (fxg_fastq_format's documented capacity) */
+typedef struct {
+    uint32_t id_mode;      /* FXG_ID_INPUT (0) | FXG_ID_ORDINAL | FXG_ID_SEQUENCE */
+    uint32_t id_both;      /* FASTQ out: the '+' line carries the new id too (fastx_renamer.c:93,97); 0: name2 as in the input */
+    uint64_t ordinal_base; /* kept record of rank k (0-based, in this block) is named base + k + 1, as "%llu" */
+    uint32_t qual_mode;    /* FXG_QUAL_AS_INPUT (0) | FXG_QUAL_ASCII | FXG_QUAL_NUMERIC */
+    uint64_t out_cap;      /* bytes d_out can take */
+    const uint16_t *d_len; /* used when d_res == NULL: every record is kept whole, its length from fxg_fastq_index */
+} fxg_format_opts;
+int  fxg_fastq_format_opts(fxg_ctx *ctx, const uint8_t *d_text, int lines_per_record, const uint32_t *d_line, uint64_t cap_lines, const uint8_t *d_flags,
+                           uint64_t records, const uint32_t *d_res, uint32_t fwd_start, int reverse, const uint8_t *d_pk_bases, const uint8_t *d_pk_qual,
+                           const uint64_t *d_pk_off, const uint8_t *d_rows_qual, uint32_t stride, int qoffset, int out_fasta, uint8_t *d_out,
+                           uint64_t *out_bytes, const fxg_format_opts *opts);
 /* FASTA records stand for `count` reads when their identifier is "id-count" (fastx.c:475-495).  weighted[0..6] = read-count
  * weighted tallies over the block: input, kept, clip too-short, adapter-only, no-adapter, adapter-found, has-N. */
 int  fxg_fasta_weights(fxg_ctx *ctx, const uint8_t *d_text, const uint32_t *d_line, uint64_t cap_lines, uint64_t records, const uint32_t *d_res,
