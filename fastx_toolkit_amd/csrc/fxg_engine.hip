@@ -479,6 +479,7 @@ extern "C" int fxg_fastq_format_opts(fxg_ctx *c, const uint8_t *d_text, int line
 {
     if (!c) return FXG_E_INVALID;
     FXG_TRY(fxg_text_format_opts_check(d_text, lines_per_record, d_line, d_flags, n, d_res, fwd_start, d_pk_bases, d_pk_qual, d_pk_off, d_rows_qual, out_fasta, d_out, out_bytes, opts, c->err, sizeof c->err));
+    FXG_TRY(fxg_text_format_source_check(d_pk_bases, reverse, fwd_start, c->err, sizeof c->err));
     if (n == 0) return FXG_OK;
     FXG_HIP(c, hipSetDevice(c->device));
     FXG_TRY(fxg_text_reserve(c, (size_t)(n + n / 512 + 4096)));

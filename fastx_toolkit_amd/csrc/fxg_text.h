@@ -425,6 +425,9 @@ struct FxgFormatArgs {
     u64 n;
     u32 fwd_start;                    // first kept base of forward outputs (fastx_trimmer -f)
     u32 rev;                          // packed outputs are reverse-complemented: their qualities are those of input positions [rl - fwd_start - len, rl - fwd_start)
+    // The quality window of record r in rows_qual, which sizes a numeric line: [fwd_start, fwd_start + len) forward, the one above when rev, and
+    // [0, len) for packed output that is not reversed (the masker keeps every read whole).  No stage chain of the engine trims and then masks, so
+    // packed, not reversed and fwd_start != 0 names no window at all: fxg_text_format_source_check refuses it.
     const uint8_t *pk_bases, *pk_qual; const u64 *pk_off;    // packed (reverse-complemented / masked) outputs, or null
     const uint8_t *rows_qual; u32 stride;                   // the batch's quality rows (Phred+33 codes): numeric output of forward records
     int qoffset;
@@ -548,28 +551,66 @@ FXG_HD u32 fxg_put_num(uint8_t *p, uint8_t c)
 // record's group.  Lane l takes the values [l * share, (l + 1) * share) and sums their widths (each value but the line's first brings its blank
 // along); an exclusive scan over the group's 16 lanes turns the sums into offsets; every lane writes its share there, the last lane the LF.
 // The scan is four __shfl_up steps of width 16: no LDS, no barrier.  All 16 lanes of a group must arrive here together: the caller's branches
-// around this call depend on the record alone (r, its res word and flags, the modes), never on the lane.  The serial form (the host pass, which
-// is what tests/emu runs lane after lane) adds up the widths before its share itself.
-FXG_HD void fxg_text_write_numeric(uint8_t *qd, const uint8_t *src, u32 len, u32 l)
+// around this call depend on the record alone (r, its res word and flags, the modes), never on the lane.  On the host a group is an array of its
+// 16 lanes' values and the same four steps run over it, so the lanes of a group go through this call in lock step there too (three phases: every
+// lane's sum, the scan, every lane's share).
+#define FXG_NUM_LANES 16u
+// the bytes lane l's share of the line takes: the widths of its values, each value but the line's first with its blank; *i0, *i1: the share
+FXG_HD u32 fxg_text_numeric_share(const uint8_t *src, u32 len, u32 l, u32 *i0, u32 *i1)
 {
     const u32 share = (len + 15u) >> 4;
-    const u32 i0 = l * share < len ? l * share : len, i1 = i0 + share < len ? i0 + share : len;
+    *i0 = l * share < len ? l * share : len;
+    *i1 = *i0 + share < len ? *i0 + share : len;
     u32 mine = 0;
-    for (u32 i = i0; i < i1; ++i) mine += fxg_num_width((int)src[i] - 33) + (i ? 1u : 0u);
+    for (u32 i = *i0; i < *i1; ++i) mine += fxg_num_width((int)src[i] - 33) + (i ? 1u : 0u);
+    return mine;
+}
+// exclusive scan over the 16 lanes of a group, Hillis-Steele in four steps.  Device: v is the lane's own value, the result its offset.
 #if defined(__HIP_DEVICE_COMPILE__)
-    u32 incl = mine;
+__device__ __forceinline__ u32 fxg_group16_excl_scan(u32 v, u32 l)
+{
+    u32 incl = v;
 #pragma unroll
     for (int d = 1; d < 16; d <<= 1) { const u32 t = __shfl_up(incl, d, 16); if ((int)l >= d) incl += t; }
-    u32 k = incl - mine;
-#else
-    u32 k = 0;
-    for (u32 i = 0; i < i0; ++i) k += fxg_num_width((int)src[i] - 33) + (i ? 1u : 0u);
+    return incl - v;
+}
 #endif
+// Host: v[16] holds the group's values and comes back as their offsets; a step reads what the step before left, as the shuffle does.
+static inline void fxg_group16_excl_scan_host(u32 (&v)[FXG_NUM_LANES])
+{
+    u32 incl[FXG_NUM_LANES];
+    for (u32 l = 0; l < FXG_NUM_LANES; ++l) incl[l] = v[l];
+    for (u32 d = 1; d < FXG_NUM_LANES; d <<= 1) {
+        u32 t[FXG_NUM_LANES];
+        for (u32 l = 0; l < FXG_NUM_LANES; ++l) t[l] = incl[l >= d ? l - d : l];      // __shfl_up: a lane below d gets its own value back
+        for (u32 l = 0; l < FXG_NUM_LANES; ++l) if (l >= d) incl[l] += t[l];
+    }
+    for (u32 l = 0; l < FXG_NUM_LANES; ++l) v[l] = incl[l] - v[l];
+}
+// lane l's share [i0, i1) written from offset k of the line on; the last lane ends the line
+FXG_HD void fxg_text_numeric_put(uint8_t *qd, const uint8_t *src, u32 i0, u32 i1, u32 k, u32 l)
+{
     for (u32 i = i0; i < i1; ++i) {
         if (i) qd[k++] = ' ';
         k += fxg_put_num(qd + k, src[i]);
     }
-    if (l == 15u) qd[k] = '\n';
+    if (l == FXG_NUM_LANES - 1u) qd[k] = '\n';
+}
+#if defined(__HIP_DEVICE_COMPILE__)
+__device__ __forceinline__ void fxg_text_write_numeric(uint8_t *qd, const uint8_t *src, u32 len, u32 l)
+{
+    u32 i0, i1;
+    const u32 mine = fxg_text_numeric_share(src, len, l, &i0, &i1);
+    fxg_text_numeric_put(qd, src, i0, i1, fxg_group16_excl_scan(mine, l), l);
+}
+#endif
+// the whole group at once (host): what the 16 lanes of the device form do together
+static inline void fxg_text_write_numeric_group(uint8_t *qd, const uint8_t *src, u32 len)
+{
+    u32 v[FXG_NUM_LANES], i0[FXG_NUM_LANES], i1[FXG_NUM_LANES];
+    for (u32 l = 0; l < FXG_NUM_LANES; ++l) v[l] = fxg_text_numeric_share(src, len, l, &i0[l], &i1[l]);
+    fxg_group16_excl_scan_host(v);
+    for (u32 l = 0; l < FXG_NUM_LANES; ++l) fxg_text_numeric_put(qd, src, i0[l], i1[l], v[l], l);
 }
 
 // 16 lanes format one kept record: "@name\nSEQ\n+name2\nQUAL\n" (FASTQ) or ">name\nSEQ\n" (FASTA).
@@ -622,7 +663,14 @@ FXG_HD void fxg_text_format_record(const FxgFormatArgs &a, u64 r, u32 l)
         else if (was_numeric) fxg_copy_bytes(qd, a.rows_qual + r * (u64)a.stride + a.fwd_start, len, l, 16, a.qoffset - 33);
         else fxg_copy_bytes(qd, a.text + o3 + a.fwd_start, len, l, 16, 0);    // R8: q + Q is the input byte
         if (l == 0) qd[len] = '\n';
-    } else fxg_text_write_numeric(qd, a.pk_bases ? a.pk_qual + po : a.rows_qual + r * (u64)a.stride + a.fwd_start, len, l);
+    } else {
+        const uint8_t *qsrc = a.pk_bases ? a.pk_qual + po : a.rows_qual + r * (u64)a.stride + a.fwd_start;
+#if defined(__HIP_DEVICE_COMPILE__)
+        fxg_text_write_numeric(qd, qsrc, len, l);
+#else
+        if (l == 0) fxg_text_write_numeric_group(qd, qsrc, len);      // host: the group's 16 lanes in lock step, once per record
+#endif
+    }
 }
 
 #ifndef FXG_HOST_EMULATION
@@ -692,6 +740,13 @@ static inline int fxg_text_format_opts_check(const uint8_t *text, int lpr, const
     const bool fastq_out = lpr == 4 && !out_fasta;
     if (pk_bases && (!pk_off || (fastq_out && !pk_qual))) FXG_PLAN_FAIL("packed output needs bases, out_off and (FASTQ) qual");
     if (fastq_out && !rows_qual) FXG_PLAN_FAIL("FASTQ output needs the batch's quality rows (numeric records are printed from them)");
+    return FXG_OK;
+}
+// The source of a format request, checked after fxg_text_format_opts_check by every entry: packed output that is not reversed is the masker's, which
+// keeps every read whole, so a first base other than 0 names no quality window (FxgFormatArgs) and is refused rather than sized from the wrong one.
+static inline int fxg_text_format_source_check(const uint8_t *pk_bases, int reverse, u32 fwd_start, char *err, size_t cap)
+{
+    if (pk_bases && !reverse && fwd_start) FXG_PLAN_FAIL("packed output that is not reversed starts at the first base: no stage chain trims and then masks");
     return FXG_OK;
 }
 // fxg_fastq_format: the input's names and encodings, and a capacity the caller vouches for (FXG_OUT_CAP_UNCHECKED)

@@ -276,7 +276,11 @@ int  fxg_fastq_pack(fxg_ctx *ctx, const uint8_t *d_text, uint64_t text_len, int 
 /* Writes "@name\nSEQ\n+name2\nQUAL\n" (or ">name\nSEQ\n": FASTA input, or out_fasta) for every kept record (res keep bit) in input
  * order.  Forward outputs are the slice [fwd_start, fwd_start + len) of the input lines; pass the engine's packed arrays + out_off
  * for reverse-complemented / masked output (reverse != 0 when they are reversed).  d_rows_qual / stride: the batch's quality rows
- * (numeric quality lines are printed from them).  d_out needs text_len + records + 16 bytes (an empty third line still gets its '+'). */
+ * (numeric quality lines are printed from them).  d_out needs text_len + records + 16 bytes (an empty third line still gets its '+').
+ * The qualities of record r that a numeric line is sized and printed from are those of its input positions [fwd_start, fwd_start + len)
+ * for forward output, [rl - fwd_start - len, rl - fwd_start) (rl: the read's length) for reversed packed output, and [0, len) for packed
+ * output that is not reversed -- the masker's, which keeps every read whole.  No stage chain trims and then masks, so packed arrays with
+ * reverse == 0 and fwd_start != 0 are refused (FXG_E_INVALID with a message). */
 int  fxg_fastq_format(fxg_ctx *ctx, const uint8_t *d_text, int lines_per_record, const uint32_t *d_line, uint64_t cap_lines, const uint8_t *d_flags,
                       uint64_t records, const uint32_t *d_res, uint32_t fwd_start, int reverse, const uint8_t *d_pk_bases, const uint8_t *d_pk_qual,
                       const uint64_t *d_pk_off, const uint8_t *d_rows_qual, uint32_t stride, int qoffset, int out_fasta, uint8_t *d_out,

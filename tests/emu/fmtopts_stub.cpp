@@ -15,6 +15,7 @@ extern "C" int fxg_fastq_format_opts(fxg_ctx *c, const uint8_t *text, int lpr, c
 {
     if (!c) return FXG_E_INVALID;
     int rc = fxg_text_format_opts_check(text, lpr, d_line, flags, n, res, fwd_start, pk_bases, pk_qual, pk_off, rows_qual, out_fasta, out, out_bytes, opts, c->err, sizeof c->err);
+    if (rc == FXG_OK) rc = fxg_text_format_source_check(pk_bases, reverse, fwd_start, c->err, sizeof c->err);
     if (rc != FXG_OK || n == 0) return rc;
     std::vector<u64> item(n);
     FxgFormatArgs a = fxg_text_format_args(text, d_line, cap_lines, flags, item.data(), n, res, fwd_start, reverse, pk_bases, pk_qual, pk_off, rows_qual, stride, qoffset, out_fasta, out);
@@ -36,3 +37,5 @@ extern "C" int fxg_fastq_format_opts(fxg_ctx *c, const uint8_t *text, int lpr, c
 
 // the closed form under the ordinal ids, for the test that holds it against a plain loop
 extern "C" uint64_t fxg_emu_dec_width_sum(uint64_t first, uint64_t count) { return fxg_dec_width_sum(first, count); }
+// a numeric quality line by the 16 lanes of a group in lock step (fxg_text_write_numeric's host form), for the test that holds it against "%d" joined by blanks
+extern "C" void fxg_emu_write_numeric(uint8_t *qd, const uint8_t *src, uint32_t len) { fxg_text_write_numeric_group(qd, src, len); }

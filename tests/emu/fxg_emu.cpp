@@ -396,7 +396,8 @@ extern "C" int fxg_emu_fastq_format(const uint8_t *text, int lpr, const uint32_t
                                     uint32_t fwd_start, int reverse, const uint8_t *pk_bases, const uint8_t *pk_qual, const uint64_t *pk_off, const uint8_t *rows_qual,
                                     uint32_t stride, int qoffset, int out_fasta, uint8_t *out, uint64_t *out_bytes, char *err, size_t cap)
 {
-    const int rc = fxg_text_format_check(text, lpr, d_line, flags, n, res, pk_bases, pk_qual, pk_off, rows_qual, out_fasta, out, out_bytes, err, cap);
+    int rc = fxg_text_format_check(text, lpr, d_line, flags, n, res, pk_bases, pk_qual, pk_off, rows_qual, out_fasta, out, out_bytes, err, cap);
+    if (rc == FXG_OK) rc = fxg_text_format_source_check(pk_bases, reverse, fwd_start, err, cap);
     if (rc != FXG_OK || n == 0) return rc;
     std::vector<u64> item(n);
     const FxgFormatArgs a = fxg_text_format_args(text, d_line, cap_lines, flags, item.data(), n, res, fwd_start, reverse, pk_bases, pk_qual, pk_off, rows_qual, stride, qoffset, out_fasta, out);

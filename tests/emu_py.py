@@ -72,6 +72,25 @@ def build_stub():
     return d
 
 
+def build_fmtopts():
+    """tests/emu/fmtopts/libfxg.so: the stub's own objects plus fxg_fastq_format_opts (fmtopts_stub.cpp) and the splitter's two entry points,
+    which engine.load_library declares (bcsplit_stub.cpp over bcsplit_emu.cpp, as tests/test_barcode_cpu.py links them).  Returns the directory."""
+    stub = build_stub()
+    d = os.path.join(_EMU, "fmtopts")
+    os.makedirs(d, exist_ok=True)
+    so = os.path.join(d, "libfxg.so")
+    srcs = [os.path.join(_EMU, f) for f in ("fmtopts_stub.cpp", "bcsplit_stub.cpp", "bcsplit_emu.cpp")]
+    base = [os.path.join(stub, "fxg_stub.o")] + _emu_objects([])
+    deps = srcs + base + _EMU_DEPS + [os.path.join(_CSRC, "fxg_barcode.h"), os.path.join(_HERE, "..", "include", "fxg.h")]
+    if not os.path.exists(so) or os.path.getmtime(so) < max(os.path.getmtime(x) for x in deps):
+        objs = [os.path.join(d, os.path.basename(x)[:-4] + ".o") for x in srcs]
+        for x, o in zip(srcs, objs):
+            subprocess.check_call(_CXX + ["-c", x, "-o", o])
+        subprocess.check_call(_LINK + base + objs + ["-o", so + ".tmp", "-ldl"])
+        os.replace(so + ".tmp", so)
+    return d
+
+
 def build_fake_rccl():
     """tests/emu/fakerccl/librccl.so.1: the five NCCL entry points the transport binds, over a shared-memory file (fake_rccl.c)."""
     d = os.path.join(_EMU, "fakerccl")
@@ -135,6 +154,51 @@ def _guarded(n, dtype=np.uint8, where="after"):
 def _alloc(n, dtype=np.uint8, guard=None):
     """_aligned() by default; guard="after" / "before": _guarded()"""
     return _aligned(n, dtype) if guard is None else _guarded(n, dtype, guard)
+
+
+def _tight(a, where):
+    """the bytes of `a` at EXACTLY their size against a guard page: the last byte is the one before the PROT_NONE page (where="after": the start is
+    then as aligned as the array's size) or the first byte the one behind it (where="before").  An empty array is an address at the guard page."""
+    raw = np.ascontiguousarray(a).view(np.uint8).reshape(-1)
+    pad = (-raw.size) % 16 if where == "after" else 0
+    g = _guarded(max(raw.size + pad, 16), np.uint8, where)
+    if raw.size == 0:
+        return g[16:] if where == "after" else g[:0]
+    g[pad:pad + raw.size] = raw
+    return g[pad:pad + raw.size]
+
+
+class FormatOpts(C.Structure):
+    _fields_ = [("id_mode", C.c_uint32), ("id_both", C.c_uint32), ("ordinal_base", C.c_uint64), ("qual_mode", C.c_uint32), ("out_cap", C.c_uint64), ("d_len", C.c_void_p)]
+
+
+_FMTOPTS = None
+
+
+def format_opts(q, guard, out_cap, id_mode=0, id_both=False, base=0, qual_mode=0, out_fasta=False):
+    """fxg_fastq_format_opts of the emulation stub (fmtopts_stub.cpp: build_fmtopts) over the arrays of a format_opts_cases.bounds_request, each at
+    exactly its size against a guard page (_tight), d_out of exactly out_cap bytes too.  guard None: plain arrays.  Returns (rc, bytes, out_bytes)."""
+    global _FMTOPTS
+    if _FMTOPTS is None:
+        L = C.CDLL(os.path.join(build_fmtopts(), "libfxg.so"))
+        vp, u64, u32, i32 = C.c_void_p, C.c_uint64, C.c_uint32, C.c_int
+        L.fxg_ctx_create.argtypes = [i32, C.POINTER(vp)]
+        L.fxg_fastq_format_opts.argtypes = [vp, vp, i32, vp, u64, vp, u64, vp, u32, i32, vp, vp, vp, vp, u32, i32, i32, vp, C.POINTER(u64), C.POINTER(FormatOpts)]
+        ctx = vp()
+        assert L.fxg_ctx_create(0, C.byref(ctx)) == 0
+        _FMTOPTS = (L, ctx)
+    L, ctx = _FMTOPTS
+    put = (lambda a: None if a is None else _tight(a, guard)) if guard else (lambda a: None if a is None else np.ascontiguousarray(a).copy())
+    arr = {k: put(q[k]) for k in ("text", "line", "flags", "lens", "rows_qual", "res", "pk_bases", "pk_qual", "pk_off")}
+    out = _tight(np.zeros(out_cap, np.uint8), guard) if guard else np.zeros(out_cap, np.uint8)
+    ptr = lambda a: None if a is None else a.__array_interface__["data"][0]      # (an empty array too: its address is the guard page's edge)
+    nb = C.c_uint64()
+    o = FormatOpts(id_mode, int(bool(id_both)), base, qual_mode, out_cap, ptr(arr["lens"]))
+    rc = L.fxg_fastq_format_opts(ctx, ptr(arr["text"]), 4, ptr(arr["line"]), q["cap_lines"], ptr(arr["flags"]), q["n"], ptr(arr["res"]), q["fwd_start"], q["reverse"],
+                                 ptr(arr["pk_bases"]), ptr(arr["pk_qual"]), ptr(arr["pk_off"]), ptr(arr["rows_qual"]), q["stride"], 33, int(out_fasta), ptr(out), C.byref(nb), C.byref(o))
+    for k in ("text", "line", "flags", "lens", "rows_qual", "res", "pk_bases", "pk_qual", "pk_off"):
+        assert arr[k] is None or np.array_equal(np.asarray(arr[k]).view(np.uint8).reshape(-1), np.ascontiguousarray(q[k]).view(np.uint8).reshape(-1)), "input %s changed" % k
+    return rc, out[:nb.value].tobytes(), nb.value
 
 
 def hist_new():

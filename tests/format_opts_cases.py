@@ -4,6 +4,11 @@ tests/test_gpu_format_opts.py runs every check here on the real engine, tests/te
 behind it (tests/emu/fmtopts_stub.cpp) -- through the same Engine methods: `StubEngine` is the Engine over that library, with its "device" tensors in
 host memory.  Every comparison is exact bytes plus out_bytes; every formatted block sits between two 4 KiB canaries that must come back untouched.
 
+Beyond the first five checks (one per mode): the source x mode matrix (check_matrix: every source the engine can produce x every mode, on inputs
+whose quality windows differ in digit count; its model pinned against pipes of the reference's own tools, check_matrix_model), the numeric
+writer beside groups of a wave that do not enter it (check_wave_mix), and the requests of the bounds tier (bounds_request: every array of a
+call at exactly its contracted size, for tests/test_emu_bounds.py and tests/test_gpu_bounds.py).
+
 The model (`expected`, and `model_rename` / `model_convert` on top of it for the two tools) works on well-formed records only: split, rename or
 re-encode, join.  tests/test_format_opts_cpu.py pins it against the reference's own fastx_renamer.c and fastq_quality_converter.c.
 """
@@ -15,6 +20,7 @@ import numpy as np
 import fxref_replay
 from fastx_toolkit_amd import engine as E
 from helpers import REPLAY, ref_driver, run_ref
+from oracle import fxoracle_py as fo
 
 CANARY, GUARD = 0xA5, 4096
 ORDINAL_BASES = [0, 8, 98, 999998, 2 ** 32 - 3, 10 ** 19 - 2]
@@ -281,6 +287,243 @@ def check_engine_method(eng):
     assert bytes(eng.fastq_format(b.d_text, b.text_len, b.ix, b.n, r.res, rows_qual=b.qual).cpu().numpy()) == expected(b.data, 4, res=res)
 
 
+# ---- the source x mode matrix ------------------------------------------------------------------------------------------------------------
+MATRIX_Q = 64                     # negative values exist at this offset only: widths of 1, 2 and 3 characters
+MATRIX_ONE_DIGIT = 17             # quality values of the first 17 positions have one digit, every later one two digits or a sign
+MATRIX_FWD_STARTS = [1, 3, 17]
+MATRIX_FIRST_BASES = [2, 4]
+MATRIX_LAST_BASE = 40             # -l 40 shortens the reads of more than 40 bases
+MATRIX_ID_MODES = [(0, False), (1, False), (1, True), (2, False), (2, True)]
+
+
+def matrix_block(numeric):
+    """200 ragged records of 1 to 70 bases at offset 64 whose quality values tell the windows of a line apart: one digit in the first
+    MATRIX_ONE_DIGIT positions, two digits or a sign and one or two digits from there on, so that a window taken from the wrong first position
+    has another digit count (matrix_windows_differ asserts it)"""
+    rng = np.random.default_rng(606)
+    out = []
+    for i in range(200):
+        L = [1, 2, 3, 4, 5, 16, 17, 18, 70, 41, 40, 39][i] if i < 12 else int(rng.integers(1, 24)) if i % 9 == 0 else int(rng.integers(24, 71))
+        s = rng.choice(np.frombuffer(b"ACGTN", np.uint8), size=L, p=[0.23, 0.23, 0.23, 0.23, 0.08]).tobytes()
+        vals = [int(rng.integers(0, 10)) if j < MATRIX_ONE_DIGIT else int(rng.integers(10, 63)) if rng.integers(0, 3) else int(rng.integers(-15, 0)) for j in range(L)]
+        name = (b"m%d %s" % (i, b"y" * 30))[:int(rng.integers(0, 31)) if i % 7 else 0]
+        num = numeric == "all" or (numeric == "alternating" and i % 2 == 1)
+        out.append(b"@" + name + b"\n" + s + b"\n" + (b"+" + name if i % 3 == 0 else b"+") + b"\n" + qual_line(vals, MATRIX_Q, num) + b"\n")
+    return b"".join(out)
+
+
+def digits(vals):
+    return sum(len(b"%d" % v) for v in vals)
+
+
+def matrix_windows_differ(data, res, right, wrong, what):
+    """the property the inputs are drawn for: in most kept records the values of the window the formatter must size, right(rl, ln), have another
+    digit count than those of each window a wrong first position would give, wrong[k](rl, ln).  Without it a wrong window is invisible."""
+    recs = records(data, 4)
+    for k, w in enumerate(wrong):
+        kept = [(qual_values(rec, MATRIX_Q), ln) for rec, (keep, ln) in zip(recs, res) if keep and ln]
+        differ = sum(digits(v[right(len(v), ln):right(len(v), ln) + ln]) != digits(v[w(len(v), ln):w(len(v), ln) + ln]) for v, ln in kept)
+        assert len(kept) > 100 and differ > len(kept) // 2, (what, k, differ, len(kept))
+
+
+def oracle_packed(data, qoffset, **pd):
+    """(res as [(keep, length)], per KEPT record (bases, values)): the block through the ORACLE's pipeline -- the model's own parse of the text into
+    rows of Phred+33 codes, then oracle/fxoracle.c's trimmer, masker or reverse complement.  Nothing here comes from the engine."""
+    recs = records(data, 4)
+    stride = max(len(rec[1]) for rec in recs)
+    b, q = np.zeros((len(recs), stride), np.uint8), np.zeros((len(recs), stride), np.uint8)
+    for k, rec in enumerate(recs):
+        b[k, :len(rec[1])] = np.frombuffer(rec[1], np.uint8)
+        q[k, :len(rec[1])] = np.array(qual_values(rec, qoffset)) + 33
+    o = fo.run_pipeline(b, q, np.array([len(rec[1]) for rec in recs], np.uint16), fo.make_params(**dict(pd, qoffset=33)))
+    res = [(int(x >> 16) & 1, int(x) & 0xFFFF) for x in o["res"]]
+    off = np.concatenate([[0], np.cumsum(o["out_len"].astype(np.int64))])
+    packed = [(o["out_bases"][off[k]:off[k + 1]].tobytes(), [int(c) - 33 for c in o["out_qual"][off[k]:off[k + 1]]]) for k in range(len(o["out_len"]))]
+    assert len(packed) == sum(k for k, _ in res)
+    return res, packed
+
+
+def slice_res(data, fwd_start):
+    """a hand-made res[] over the forward slices from fwd_start on: reads too short for it and one record in five dropped, the kept ones to their end,
+    one or two bases short of it, or (one in eleven) of length 0"""
+    res = []
+    for k, rec in enumerate(records(data, 4)):
+        rl = len(rec[1])
+        res.append((0, 0) if rl < fwd_start or k % 5 == 4 else (1, 0 if k % 11 == 3 else max(0, rl - fwd_start - k % 3)))
+    return res
+
+
+def matrix_sources(eng, b):
+    """name, fmt() arguments, expected() arguments of every source the engine can produce, each with the window property asserted"""
+    T, out = eng.torch, []
+    whole = [(1, len(rec[1])) for rec in records(b.data, 4)]
+    out.append(("whole", dict(), dict()))
+    for fs in MATRIX_FWD_STARTS:
+        res = slice_res(b.data, fs)
+        assert sum(1 for k, ln in res if k and ln == 0) >= 5
+        matrix_windows_differ(b.data, res, lambda rl, ln: fs, [lambda rl, ln: 0], ("slice", fs))
+        d_res = T.tensor([(k << 16) | ln for k, ln in res], dtype=T.int32, device=eng.device)
+        out.append(("slice%d" % fs, dict(res=d_res, fwd_start=fs), dict(res=res, fwd_start=fs)))
+    r, eres = run(eng, b, compact=True, stages=0x40, mask_min_quality=20, mask_char="N")
+    res, packed = oracle_packed(b.data, MATRIX_Q, stages=0x40, mask_min_quality=20, mask_char="N")
+    assert res == whole == eres and any(s != rec[1] for (s, _), rec in zip(packed, records(b.data, 4)))
+    out.append(("masked", dict(res=r.res, packed=(r.out_bases, r.out_qual, r.out_off)), dict(res=res, packed=packed)))
+    r, eres = run(eng, b, compact=True, stages=0x08)
+    res, packed = oracle_packed(b.data, MATRIX_Q, stages=0x08)
+    assert res == whole == eres
+    out.append(("reversed", dict(res=r.res, packed=(r.out_bases, r.out_qual, r.out_off), reverse=True), dict(res=res, packed=packed)))
+    for first in MATRIX_FIRST_BASES:
+        pd = dict(stages=0x18, ft_first=first, ft_last=MATRIX_LAST_BASE)
+        r, eres = run(eng, b, compact=True, **pd)
+        res, packed = oracle_packed(b.data, MATRIX_Q, **pd)
+        assert res == eres and 0 < sum(1 for (k, ln), (_, rl) in zip(res, whole) if k and rl > MATRIX_LAST_BASE and ln == MATRIX_LAST_BASE - first + 1) < sum(k for k, _ in res) < b.n
+        fs = first - 1
+        matrix_windows_differ(b.data, res, lambda rl, ln: rl - fs - ln, [lambda rl, ln: fs, lambda rl, ln: 0], ("reversed", first))
+        out.append(("reversed%d" % first, dict(res=r.res, fwd_start=fs, packed=(r.out_bases, r.out_qual, r.out_off), reverse=True), dict(res=res, packed=packed)))
+    return out
+
+
+def check_matrix(eng, numeric):
+    """6. every source the engine can produce x every mode: forward whole (d_len), forward slices from the 2nd, 4th and 18th base on under a hand-made
+    res[], the masker's packed output, the reverse complement's, the reverse complement trimmed to bases 2..40 and 4..40; ids as in the input, ordinal
+    and sequence with id_both on and off; the three quality modes; FASTQ and FASTA out.  A fixed trim followed by the masker is no source: the
+    engine has no such stage chain (check_requests holds both refusals)."""
+    b = Block(eng, matrix_block(numeric), qoffset=MATRIX_Q)
+    assert b.n == 200
+    for name, fkw, ekw in matrix_sources(eng, b):
+        for id_mode, both in MATRIX_ID_MODES:
+            for out_fasta, qual_mode in ((False, 0), (False, 1), (False, 2), (True, 0)):
+                kw = dict(out_fasta=out_fasta, id_mode=id_mode, id_both=both, base=10 ** 7 - 50, qual_mode=qual_mode)
+                same(fmt(eng, b, **fkw, **kw), expected(b.data, 4, MATRIX_Q, **ekw, **kw), (name, numeric, kw))
+
+
+WAVE_KINDS = ["numeric", "character", "dropped", "numeric_empty"]
+
+
+def check_wave_mix(eng):
+    """7. the 16-lane numeric writer beside groups that do not enter it.  A wave of the format kernel holds the groups of four consecutive records,
+    and the writer's shuffles are only right if whole groups take its branch: every wave here holds one record that goes out as numbers, one that
+    goes out as characters, one dropped and one kept at length 0 whose line is numeric, in each of the four rotations, at the lengths around the
+    per-lane shares (QUAL_LENGTHS).  As the input has it (the mix proper), then all as numbers and all as characters."""
+    out, res, at, span = [], [], 0, list(range(0, 94))
+    for rot in range(4):
+        for L in QUAL_LENGTHS:
+            for slot in range(4):
+                kind = WAVE_KINDS[(slot + rot) % 4]
+                vals = [span[(at + 3 * j) % len(span)] for j in range(L)]
+                at += 11
+                if L == 1 and kind != "character":
+                    vals = [10 + vals[0] % 80]                 # (one value of one digit would read back as a character)
+                out.append(b"@w%d\n%s\n+%s\n%s\n" % (len(out), b"ACGTN"[len(out) % 5:][:1] * L, b"x" if slot % 2 else b"", qual_line(vals, 33, kind != "character")))
+                res.append((0, L) if kind == "dropped" else (1, 0) if kind == "numeric_empty" else (1, L))
+    b = Block(eng, b"".join(out))
+    assert b.n == 16 * len(QUAL_LENGTHS) and b.n % 4 == 0
+    flags = b.ix.flags[:b.n].cpu().numpy()
+    for w in range(b.n // 4):                                  # every wave: the four kinds, as the index sees them
+        kinds = sorted((int(flags[4 * w + k]) & 1, res[4 * w + k]) for k in range(4))
+        L = max(ln for _, ln in res[4 * w:4 * w + 4])
+        assert kinds == sorted([(1, (1, L)), (0, (1, L)), (1, (0, L)), (1, (1, 0))]), (w, kinds)
+    d_res = eng.torch.tensor([(k << 16) | ln for k, ln in res], dtype=eng.torch.int32, device=eng.device)
+    for mode in (E.QUAL_AS_INPUT, E.QUAL_NUMERIC, E.QUAL_ASCII):
+        for id_mode, both in ((0, False), (1, True)):
+            kw = dict(qual_mode=mode, id_mode=id_mode, id_both=both, base=98)
+            same(fmt(eng, b, res=d_res, **kw), expected(b.data, 4, res=res, **kw), ("wave mix", kw))
+
+
+# ---- the bounds tier's requests (tests/test_emu_bounds.py: guard pages; tests/test_gpu_bounds.py: poison and canaries) -------------------------
+BOUNDS_LENGTHS = [150, 1, 15, 16, 17, 31, 32, 33]
+BOUNDS_LAST = {"longest": 150, "multiple": 32, "one": 1}          # the last record in turn: the longest (its quality window ends the row array), a multiple of 16, one base
+BOUNDS_SOURCES = {"whole": None, "slice3": 3, "slice17": 17, "masked": dict(stages=0x40, mask_min_quality=20, mask_char="N"), "reversed": dict(stages=0x08),
+                  "reversed2": dict(stages=0x18, ft_first=2, ft_last=140), "reversed4": dict(stages=0x18, ft_first=4, ft_last=140)}
+BOUNDS_MODES = {         # name: (the modes, the input's quality lines)
+    "ordinal": (dict(id_mode=1, id_both=True, base=10 ** 19 - 2), "alternating"),       # 20-digit ids, written backwards by lanes 1 and 2
+    "sequence": (dict(id_mode=2, id_both=True), "alternating"),                         # the bases read twice more
+    "numeric": (dict(qual_mode=2), "alternating"),                                      # the size pass's window, the writer's last-lane LF
+    "ascii": (dict(qual_mode=1), "all"),                                                # characters from the rows of numeric input
+}
+
+
+def bounds_block(last, numeric):
+    """37 records of the lengths BOUNDS_LENGTHS in turn, the last one of `last` bases; every quality value 0..93"""
+    out, at, span = [], 0, list(range(94))
+    for i in range(37):
+        L = last if i == 36 else BOUNDS_LENGTHS[i % len(BOUNDS_LENGTHS)]
+        vals = [span[(at + 5 * j) % 94] for j in range(L)]
+        at += 13
+        num = numeric == "all" or (numeric == "alternating" and i % 2 == 0)
+        if L == 1 and num:
+            vals = [10 + vals[0] % 80]
+        name = (b"b%d %s" % (i, b"z" * 20))[:(i * 5) % 21]
+        out.append(b"@" + name + b"\n" + bytes(b"ACGTN"[(i + j) % 5] for j in range(L)) + b"\n" + (b"+" + name if i % 2 else b"+") + b"\n" + qual_line(vals, 33, num) + b"\n")
+    return b"".join(out)
+
+
+def bounds_request(data, source):
+    """Every array of an fxg_fastq_format_opts call over `data` as a host array of exactly its contracted size (include/fxg.h) -- the line index,
+    lengths, flags and quality rows written down from the text by the model, the packed arrays from the oracle -- plus expected()'s arguments."""
+    recs = records(data, 4)
+    n, stride = len(recs), max(len(rec[1]) for rec in recs)
+    nl = np.flatnonzero(np.frombuffer(data, np.uint8) == 10)
+    cap_lines = 4 * n + 1
+    assert len(nl) == 4 * n and stride == 150
+    line = np.zeros(2 * cap_lines, np.uint32)
+    line[1:cap_lines], line[cap_lines:cap_lines + 4 * n] = nl + 1, nl
+    rows = np.zeros((n, stride), np.uint8)
+    for k, rec in enumerate(recs):
+        rows[k, :len(rec[1])] = np.array(qual_values(rec, 33)) + 33
+    q = dict(n=n, stride=stride, cap_lines=cap_lines, text_len=len(data), text=np.frombuffer(data + bytes(16), np.uint8).copy(), line=line,
+             flags=np.array([len(rec[3]) != len(rec[1]) for rec in recs], np.uint8), lens=np.array([len(rec[1]) for rec in recs], np.uint16),
+             rows_qual=rows.reshape(-1), res=None, fwd_start=0, reverse=0, pk_bases=None, pk_qual=None, pk_off=None, ekw=dict())
+    pd = BOUNDS_SOURCES[source]
+    if isinstance(pd, int):
+        res = [(0, 0) if len(rec[1]) < pd or k % 5 == 3 else (1, 0 if k % 7 == 2 else len(rec[1]) - pd) for k, rec in enumerate(recs)]
+        q.update(fwd_start=pd, ekw=dict(res=res, fwd_start=pd))
+    elif pd is not None:
+        res, packed = oracle_packed(data, 33, **pd)
+        lens = np.array([len(s) for s, _ in packed], np.int64)
+        q.update(reverse=int(bool(pd["stages"] & 8)), fwd_start=pd.get("ft_first", 1) - 1, pk_bases=np.frombuffer(b"".join(s for s, _ in packed), np.uint8).copy(),
+                 pk_qual=np.array([v + 33 for _, vals in packed for v in vals], np.uint8), pk_off=np.concatenate([[0], np.cumsum(lens)[:-1]]).astype(np.uint64),
+                 ekw=dict(res=res, packed=packed))
+    if pd is not None:
+        q["res"] = np.array([(k << 16) | ln for k, ln in res], np.uint32)
+        if len(recs[-1][1]) == stride and source in ("slice3", "slice17", "masked", "reversed"):      # the last window ends with the last byte of the rows
+            assert res[-1] == (1, stride - q["fwd_start"])
+    return q
+
+
+def matrix_reference_jobs(numeric):
+    """(pipe of reference tools, what the model says): the combinations of the matrix that the reference's own tools can express, which pin the model
+    (expected over oracle_packed) against the real libfastx.  Its tools write a record in the encoding it came in, and fastq_to_fasta -r numbers."""
+    data = matrix_block(numeric)
+    Q = ["-Q", str(MATRIX_Q)]
+    jobs = []
+    for fs in MATRIX_FWD_STARTS:
+        res, _ = oracle_packed(data, MATRIX_Q, stages=0x10, ft_first=fs + 1)
+        assert res == [(int(len(rec[1]) > fs), len(rec[1]) - fs if len(rec[1]) > fs else r[1]) for rec, r in zip(records(data, 4), res)]
+        jobs.append(([["fastx_trimmer", "-f", str(fs + 1)] + Q], expected(data, 4, MATRIX_Q, res=res, fwd_start=fs)))
+        jobs.append(([["fastx_trimmer", "-f", str(fs + 1)] + Q, ["fastq_to_fasta", "-n", "-r"] + Q], expected(data, 4, MATRIX_Q, res=res, fwd_start=fs, out_fasta=True, id_mode=E.ID_ORDINAL)))
+    res, packed = oracle_packed(data, MATRIX_Q, stages=0x40, mask_min_quality=20, mask_char="N")
+    jobs.append(([["fastq_masker", "-q", "20"] + Q], expected(data, 4, MATRIX_Q, res=res, packed=packed)))
+    res, packed = oracle_packed(data, MATRIX_Q, stages=0x08)
+    jobs.append(([["fastx_reverse_complement"] + Q], expected(data, 4, MATRIX_Q, res=res, packed=packed)))
+    for first in MATRIX_FIRST_BASES:
+        res, packed = oracle_packed(data, MATRIX_Q, stages=0x18, ft_first=first, ft_last=MATRIX_LAST_BASE)
+        pipe = [["fastx_reverse_complement"] + Q, ["fastx_trimmer", "-f", str(first), "-l", str(MATRIX_LAST_BASE)] + Q]
+        jobs.append((pipe, expected(data, 4, MATRIX_Q, res=res, packed=packed)))
+        jobs.append((pipe + [["fastq_to_fasta", "-n", "-r"] + Q], expected(data, 4, MATRIX_Q, res=res, packed=packed, out_fasta=True, id_mode=E.ID_ORDINAL)))
+    return data, jobs
+
+
+def check_matrix_model(numeric):
+    data, jobs = matrix_reference_jobs(numeric)
+    for pipe, want in jobs:
+        out = data
+        for argv in pipe:
+            rc, out, err = reference(argv, out)
+            assert rc == 0, (pipe, argv, err)
+        assert out == want, (numeric, pipe)
+
+
 # ---- refused requests (in the way of tests/request_cases.py: the code and the fxg_last_error text of each, literal) ----------------------
 REFUSALS = [
     # name, keyword arguments of fmt(), fxg_last_error (None: a bare FXG_E_INVALID)
@@ -289,6 +532,9 @@ REFUSALS = [
     ("unknown_qual_mode", dict(qual_mode=3), "unknown quality mode 3"),
     ("no_res_with_first_base", dict(fwd_start=2), "without res every record is kept whole: no packed output and no first base"),
     ("ordinals_past_u64", dict(id_mode=1, base=2 ** 64 - 2), "ordinal ids from 18446744073709551615 on pass 2^64 - 1"),
+    # ("masker": the res and the packed arrays of a masker run over the block)
+    ("masked_with_first_base", dict(packed="masker", fwd_start=2), "packed output that is not reversed starts at the first base: no stage chain trims and then masks"),
+    ("masked_with_first_base_numeric", dict(packed="masker", fwd_start=2, qual_mode=2, id_mode=1), "packed output that is not reversed starts at the first base: no stage chain trims and then masks"),
 ]
 
 
@@ -301,7 +547,15 @@ def check_requests(eng):
         same(fmt(eng, b, cap=len(want), **kw), want, ("exact capacity", kw))
         rc, _, _ = fmt(eng, b, cap=len(want) - 1, **kw)
         assert rc == -1 and eng.lib.fxg_last_error(eng.ctx).decode() == "the formatted block needs %d bytes, d_out takes %d" % (len(want), len(want) - 1), kw
+    masked, _ = run(eng, b, compact=True, stages=0x40, mask_min_quality=20, mask_char="N")
+    try:                                                       # a fixed trim and then the masker: no stage chain of the engine, so no packed output of that kind exists
+        run(eng, b, compact=True, stages=0x10 | 0x40, ft_first=3, mask_min_quality=20, mask_char="N")
+        raise AssertionError("the engine ran a fixed trim followed by the masker: the formatter's refusal of that source no longer holds")
+    except E.FxgError as e:
+        assert "unsupported stage chain 0x50" in str(e), e
     for name, kw, text in REFUSALS:
+        if kw.get("packed") == "masker":
+            kw = dict(kw, res=masked.res, packed=(masked.out_bases, masked.out_qual, masked.out_off))
         rc, _, _ = fmt(eng, b, cap=1 << 16, **kw)
         assert rc == -1 and (text is None or eng.lib.fxg_last_error(eng.ctx).decode() == text), (name, rc, eng.lib.fxg_last_error(eng.ctx))
     nb, o = C.c_uint64(), E.FxgFormatOpts(0, 0, 0, 0, 1 << 20, None)          # neither res nor lengths; no opts at all

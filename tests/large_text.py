@@ -309,6 +309,27 @@ class Block:
             sz = sz + t.clamp(f["c2"] - 1, min=0) + ln + 3
         return t.where(keep, sz, 0)
 
+    def numeric_line(self, rr):
+        """(bytes of the record's quality line written as numbers -- "%d" joined by single blanks --, how many of its values are -1: the code of a
+        blank) for FASTQ records, from the quality hash alone"""
+        t = self.torch
+        f = self.fields(rr)
+        i = t.arange(STRIDE, dtype=t.int64, device=rr.device)[None, :]
+        inside = i < f["L"][:, None]
+        code, _ = self.qual_value(rr[:, None], f["numeric"][:, None], i)
+        v = code - 33
+        width = (v < 0).to(t.int64) + t.where(t.abs(v) >= 10, 2, 1)
+        return (width * inside).sum(1) + f["L"] - 1, ((code == 32) & inside).sum(1)
+
+    def mode_sizes(self, rr, mode, base=0):
+        """bytes fxg_fastq_format_opts writes for each FASTQ record kept whole, rank = index: "numeric-ordinal" = numeric quality lines and the
+        ordinal id base + index + 1 on both name lines; "ascii-sequence" = character quality lines and the bases on both name lines"""
+        L = self.fields(rr)["L"]
+        if mode == "ascii-sequence":
+            return 4 * L + 6
+        assert mode == "numeric-ordinal"
+        return 2 * _ord_parts(self.torch, base, rr)[2] + L + self.numeric_line(rr)[0] + 6
+
     def weights(self, rr, res):
         """the seven tallies of fxg_fasta_weights over the records rr, as int64 sums"""
         t = self.torch
@@ -352,6 +373,81 @@ def size_rule(torch, shape, device="cpu", cap=CAP, seed=SEED, slab=4_000_000):
         if int(S[n - 1 - base]) + int(sizes(torch.tensor([n - 1], dtype=torch.int64, device=device), n)[0]) <= cap:
             return n
     raise AssertionError("no N for %s" % shape)
+
+
+# ---- ordinal ids over more than 2^24 kept records ------------------------------------------------------------------------------------------
+# The format's scan carries a record's rank in 24 bits; fxg_text_rank rebuilds it at every 2^23-th record, and the rank feeds the ordinal id and
+# the closed-form digit offset.  The smallest block that crosses both: 2^24 + 2^23 + 5 records of four bytes (">\nA\n"; as FASTQ "@\nA\n+\nI\n"),
+# fifteen in sixteen kept by a hash or all of them -- the kept count passes 2^24 between two 2^23 steps -- and three levels of the scan.
+ORD_N = (1 << 24) + (1 << 23) + 5
+# the second base: the ids reach nine digits with the rank 2^24 - 1, so every rank from the wrap on has another width than the rank modulo 2^24
+# (10^8 is the first power of ten above 2^24: no base puts 10^7 there)
+ORD_BASES = [0, 10 ** 8 - 2 ** 24, 10 ** 19 - 2]
+ORD_RECORD = {2: b">\nA\n", 4: b"@\nA\n+\nI\n"}
+_P = 10 ** 10
+
+
+def ord_keep(torch, rr):
+    """the hash-chosen fifteen records in sixteen"""
+    return _bits(_mix(rr + 0x5EED), 11, 4) != 0
+
+
+def dec_width_sum(first, count):
+    """the decimal digits of first .. first + count - 1 together, in Python's integers (what fxg_dec_width_sum states in closed form)"""
+    total, lo, w, last = 0, 0, 1, first + count - 1
+    while count and lo <= last:
+        hi = 10 ** w - 1
+        if hi >= first:
+            total += w * (min(last, hi) - max(first, lo) + 1)
+        lo, w = hi + 1, w + 1
+    return total
+
+
+def ord_offset(base, k, fastq_both):
+    """the output byte at which the kept record of rank k begins: ">id\nA\n", or "@id\nA\n+id\nI\n" with the id on both lines"""
+    return (8 * k + 2 * dec_width_sum(base + 1, k)) if fastq_both else (4 * k + dec_width_sum(base + 1, k))
+
+
+def _ord_parts(torch, base, kk):
+    """id = base + 1 + kk, which passes 2^63, as (high part, low ten digits, width)"""
+    lo = (base + 1) % _P + kk
+    carry = (lo >= _P).to(torch.int64)
+    lo, hi = lo - carry * _P, (base + 1) // _P + carry
+    return hi, lo, torch.where(hi > 0, 10 + ndigits(torch, hi), ndigits(torch, lo))
+
+
+def ord_text(torch, base, k0, k1, fastq_both, device="cpu"):
+    """uint8 tensor: the formatted records of the kept ranks k0 .. k1 - 1, one after the other"""
+    kk = torch.arange(k0, k1, dtype=torch.int64, device=device)
+    hi, lo, w = _ord_parts(torch, base, kk)
+    sz = 2 * w + 8 if fastq_both else w + 4
+    rec = torch.repeat_interleave(torch.arange(k1 - k0, dtype=torch.int64, device=device), sz)
+    off = torch.arange(rec.numel(), dtype=torch.int64, device=device) - (torch.cumsum(sz, 0) - sz)[rec]
+    hi, lo, w = hi[rec], lo[rec], w[rec]
+    second = off >= w + 5                                      # (FASTQ: the '+' line's copy)
+    j = torch.where(second, off - w - 5, off - 1) if fastq_both else off - 1
+    p = torch.clamp(w - 1 - j, 0, 19)
+    p10 = torch.tensor(_P10[:10], dtype=torch.int64, device=device)
+    digit = 48 + torch.where(p < 10, torch.div(lo, p10[torch.clamp(p, 0, 9)], rounding_mode="floor"), torch.div(hi, p10[torch.clamp(p - 10, 0, 9)], rounding_mode="floor")) % 10
+    if not fastq_both:
+        ch = torch.where(off == 0, 62, torch.where(off <= w, digit, torch.where(off == w + 2, 65, 10)))
+    else:
+        fixed = torch.where(off == 0, 64, torch.where(off == w + 2, 65, torch.where(off == w + 4, 43, torch.where(off == 2 * w + 6, 73, 10))))
+        ch = torch.where(((off >= 1) & (off <= w)) | ((off >= w + 5) & (off <= 2 * w + 4)), digit, fixed)
+    return ch.to(torch.uint8)
+
+
+def ord_index(np_, n, lpr):
+    """the line index of n records ORD_RECORD[lpr] as fxg_fastq_index makes it: (line u32 [2 * cap_lines], cap_lines)"""
+    cap_lines = lpr * n + 1
+    line = np_.zeros(2 * cap_lines, np_.uint32)
+    rec = len(ORD_RECORD[lpr])
+    r = np_.arange(n, dtype=np_.uint64) * np_.uint64(rec)
+    for k in range(lpr):                                       # line k of a record: the prefix line has one byte, the others one too ('+' and 'I')
+        line[k:lpr * n:lpr] = r + np_.uint64(2 * k)
+        line[cap_lines + k:cap_lines + lpr * n:lpr] = r + np_.uint64(2 * k + 1)
+    line[lpr * n] = rec * n
+    return line, cap_lines
 
 
 def crossed(nbytes):

@@ -122,6 +122,13 @@ def _cases():
                 for at_eof in (0, 1):
                     add("text.l%d.n%d.m%d.nl%d.eof%d" % (lpr, n, maxlen, final_nl, at_eof), kind="text", lpr=lpr, n=n, maxlen=maxlen, final_nl=final_nl,
                         at_eof=at_eof, guard="after" if (n + at_eof) % 2 else "before")
+    # ---- the formatter's output modes (fxg_fastq_format_opts): every source kind x mode x last record, both guard sides ----
+    import format_opts_cases as F
+    for source in F.BOUNDS_SOURCES:
+        for mode in F.BOUNDS_MODES:
+            for last in F.BOUNDS_LAST:
+                for guard in ("after", "before"):
+                    add("fmtopts.%s.%s.%s.%s" % (source, mode, last, guard), kind="fmtopts", source=source, mode=mode, last=last, guard=guard)
     return cs
 
 
@@ -235,10 +242,26 @@ def _run_text(c):
         assert w[0] == full and w[1] == full, w
 
 
+def _run_fmtopts(c):
+    """d_len as u16[n] (res null), the size pass's quality window of every source kind, pk_qual / pk_bases in whole 16-byte chunks and a byte tail,
+    the bases read again for sequence ids, 20-digit ordinals, the numeric writer's LF: every array at exactly its size against the guard page,
+    d_out at exactly out_bytes -- learnt from a first run into a roomy d_out (the inputs guarded there too), which is also compared with the model"""
+    import emu_py as emu
+    import format_opts_cases as F
+    kw, numeric = F.BOUNDS_MODES[c["mode"]]
+    data = F.bounds_block(F.BOUNDS_LAST[c["last"]], numeric)
+    q = F.bounds_request(data, c["source"])
+    want = F.expected(data, 4, 33, **q["ekw"], **kw)
+    rc, out, nb = emu.format_opts(q, c["guard"], len(data) * 8, **kw)
+    assert rc == 0 and nb == len(want) and out == want, ("a roomy d_out", rc, nb, len(want))
+    rc, out, nb = emu.format_opts(q, c["guard"], nb, **kw)
+    assert rc == 0 and nb == len(want) and out == want, ("d_out of exactly out_bytes", rc, nb, len(want))
+
+
 def run_case(c):
     os.environ.update(c["env"])
     sys.path[:0] = [ROOT, HERE]
-    {"pipe": _run_pipe, "qstats": _run_qstats, "text": _run_text}[c.get("kind", "pipe")](c)
+    {"pipe": _run_pipe, "qstats": _run_qstats, "text": _run_text, "fmtopts": _run_fmtopts}[c.get("kind", "pipe")](c)
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------
@@ -259,6 +282,7 @@ def outcomes():
     import emu_py as emu
     from oracle import fxoracle_py as fo
     emu.build()                     # once, here: the children only load the library
+    emu.build_fmtopts()
     fo.lib()
     try:
         cpus = len(os.sched_getaffinity(0))

@@ -31,20 +31,12 @@ GALAXY = [      # argv, input, expected output (the reference's Galaxy test pair
 
 
 @pytest.fixture(scope="module")
-def stubdir(tmp_path_factory):
-    """a libfxg.so of the stub's own objects plus fxg_fastq_format_opts (fmtopts_stub.cpp) and the splitter's two entry points, which
-    engine.load_library declares (bcsplit_stub.cpp over bcsplit_emu.cpp, as tests/test_barcode_cpu.py links them)"""
+def stubdir():
+    """a libfxg.so of the stub's own objects plus fxg_fastq_format_opts (emu_py.build_fmtopts)"""
     from fastx_toolkit_amd import build as b
-    stub = emu_py.build_stub()
     b.build_engine()          # the tools link against the real library's soname; a stub replaces it at run time only
     b.build_host()
-    d = str(tmp_path_factory.mktemp("fmtopts"))
-    objs = []
-    for src in ("fmtopts_stub.cpp", "bcsplit_stub.cpp", "bcsplit_emu.cpp"):
-        objs.append(os.path.join(d, src[:-4] + ".o"))
-        subprocess.check_call(emu_py._CXX + ["-c", os.path.join(EMU_DIR, src), "-o", objs[-1]])
-    subprocess.check_call(emu_py._LINK + [os.path.join(stub, "fxg_stub.o")] + objs + emu_py._emu_objects([]) + ["-o", os.path.join(d, "libfxg.so"), "-ldl"])
-    return d
+    return emu_py.build_fmtopts()
 
 
 @pytest.fixture(scope="module")
@@ -106,6 +98,46 @@ def test_requests(eng):
 
 def test_engine_method(eng):
     F.check_engine_method(eng)
+
+
+@pytest.mark.parametrize("numeric", ["none", "all", "alternating"])
+def test_source_mode_matrix(eng, numeric):
+    F.check_matrix(eng, numeric)
+
+
+def test_numeric_writer_beside_other_groups_of_a_wave(eng):
+    F.check_wave_mix(eng)
+
+
+@pytest.mark.parametrize("numeric", ["none", "all", "alternating"])
+def test_matrix_model_against_the_reference_tools(numeric):
+    """the model behind the matrix (expected over the oracle's trimmed, masked and reversed records) against pipes of the real libfastx's tools"""
+    F.check_matrix_model(numeric)
+
+
+def test_numeric_writer_lanes_in_lock_step(stubdir):
+    """fxg_text_write_numeric's host form: the 16 lanes of a group together -- every lane's share and sum, the four-step scan over the group's 16
+    values, every lane's write, the last lane's LF -- against "%d" joined by blanks.  Every length from 0 to 70 and around 256, 4 096, the longest
+    read and 65 535; values cycling through -15..93 with three strides; the codes and the line each between two PROT_NONE pages, so a lane that
+    reads past its share or writes past the line's LF faults."""
+    L = C.CDLL(os.path.join(stubdir, "libfxg.so"))
+    L.fxg_emu_write_numeric.restype, L.fxg_emu_write_numeric.argtypes = None, [C.c_void_p, C.c_void_p, C.c_uint32]
+    span = list(range(-15, 94))
+    for n in list(range(71)) + [255, 256, 257, 4095, 4096, 4097, 24999, 65535]:
+        for stride in (1, 7, 40):
+            vals = [span[(n + j * stride) % len(span)] for j in range(n)]
+            want = b" ".join(b"%d" % v for v in vals) + b"\n"
+            for where in ("after", "before"):
+                # (_guarded rounds a range up to the 16-byte granule: the arrays end exactly at the page when their size is a multiple of 16,
+                # so the line is padded in FRONT to one -- the LF is then the byte before the guard page)
+                pad = (-len(want)) % 16 if where == "after" else 0
+                buf = emu_py._guarded(len(want) + pad, np.uint8, where)
+                spad = (-n) % 16 if where == "after" else 0
+                sbuf = emu_py._guarded(n + spad, np.uint8, where)
+                sbuf[spad:] = np.array(vals, np.int64) + 33
+                buf[:] = 0xA5
+                L.fxg_emu_write_numeric(buf.ctypes.data + pad, sbuf.ctypes.data + spad, n)
+                assert buf[pad:].tobytes() == want and (buf[:pad] == 0xA5).all(), (n, stride, where)
 
 
 # ---- the model against the reference's own sources ---------------------------------------------------------------------------------------

@@ -58,6 +58,7 @@ def _base_poison(c):
 PIPE = [c for c in eb.CASES if c.get("kind", "pipe") == "pipe" and c["guard"] == "after"]
 QSTATS = [c for c in eb.CASES if c.get("kind") == "qstats"]
 TEXT = [c for c in eb.CASES if c.get("kind") == "text" and c["at_eof"] == 1]
+FMTOPTS = [c for c in eb.CASES if c.get("kind") == "fmtopts" and c["guard"] == "after"]
 
 
 @pytest.mark.parametrize("case", PIPE, ids=[c["name"] for c in PIPE])
@@ -169,3 +170,38 @@ def test_text_poison_and_canaries(engine, case):
     engine.sync()
     for name, f in (("text", ft), ("line", fline), ("len", flen), ("flags", fflags), ("bases", fb), ("res", fres), ("out", fout)) + ((("qual", fq),) if fq else ()):
         f.check("%s: %s" % (case["name"], name))
+
+
+@pytest.mark.parametrize("case", FMTOPTS, ids=[c["name"] for c in FMTOPTS])
+def test_format_opts_poison_and_canaries(engine, case):
+    """fxg_fastq_format_opts with every array a view of exactly its contracted size: d_len of n values, the quality rows of n * stride bytes, the
+    packed arrays of the kept bytes and records, res, flags, the line index, and d_out of exactly out_bytes (learnt from a first run into a roomy
+    one).  Poison around the inputs -- lengths of 65 535, quality codes of one and two digits, kept res words, numeric flags, line offsets of
+    0xA55AC33C -- would change the size or the text; the sentinel around both outputs must come back unchanged."""
+    import format_opts_cases as F
+    from fastx_toolkit_amd.engine import FxgFormatOpts
+    kw, numeric = F.BOUNDS_MODES[case["mode"]]
+    data = F.bounds_block(F.BOUNDS_LAST[case["last"]], numeric)
+    q = F.bounds_request(data, case["source"])
+    want = F.expected(data, 4, 33, **q["ekw"], **kw)
+    before = engine.scan_recoveries()
+    poison = dict(text=b"\n@p\nAC\n+\nII\n>q\nGT\n", line=SENTINEL, flags=b"\x01", lens=b"\xff\xff", rows_qual=QPOISON, res=b"\x96\x00\x01\x00", pk_bases=b"NxnAC@", pk_qual=QPOISON,
+                  pk_off=b"\xff" * 8)
+    f = {k: Framed(engine, q[k].nbytes, poison[k], q[k]) for k in poison if q[k] is not None}
+    ptr = lambda k: f[k].view.data_ptr() if k in f else None
+    outs = []
+    for cap in (8 * len(data), len(want)):
+        fout = Framed(engine, cap, SENTINEL)
+        nb = C.c_uint64()
+        o = FxgFormatOpts(kw.get("id_mode", 0), int(kw.get("id_both", False)), kw.get("base", 0), kw.get("qual_mode", 0), cap, ptr("lens"))
+        engine._after_torch()
+        rc = engine.lib.fxg_fastq_format_opts(engine.ctx, ptr("text"), 4, ptr("line"), q["cap_lines"], ptr("flags"), q["n"], ptr("res"), q["fwd_start"], q["reverse"], ptr("pk_bases"),
+                                              ptr("pk_qual"), ptr("pk_off"), ptr("rows_qual"), q["stride"], 33, 0, fout.view.data_ptr(), C.byref(nb), C.byref(o))
+        engine._before_torch()
+        engine._check(rc)
+        engine.sync()
+        assert nb.value == len(want) and fout.view[:nb.value].cpu().numpy().tobytes() == want, (case["name"], cap, nb.value, len(want))
+        outs.append(fout)
+    for name, fr in list(f.items()) + [("out, roomy", outs[0]), ("out, exact", outs[1])]:
+        fr.check("%s: %s" % (case["name"], name))
+    assert engine.scan_recoveries() == before

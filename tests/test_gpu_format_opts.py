@@ -45,6 +45,19 @@ def test_engine_method(engine):
     F.check_engine_method(engine)
 
 
+@pytest.mark.parametrize("numeric", ["none", "all", "alternating"])
+def test_source_mode_matrix(engine, numeric):
+    before = engine.scan_recoveries()
+    F.check_matrix(engine, numeric)
+    assert engine.scan_recoveries() == before
+
+
+def test_numeric_writer_beside_other_groups_of_a_wave(engine):
+    before = engine.scan_recoveries()
+    F.check_wave_mix(engine)
+    assert engine.scan_recoveries() == before
+
+
 # ---- the tools on the real engine ------------------------------------------------------------------------------------------------------
 @pytest.fixture(scope="module")
 def tools():

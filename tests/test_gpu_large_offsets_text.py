@@ -257,11 +257,11 @@ def _newlines(torch, t, step=1 << 30):
     return sum(int((t[s:s + step] == 10).sum()) for s in range(0, t.numel(), step))
 
 
-def _format_windows(eng, name, c, out, out_start, expect, extra_marks=True):
+def _format_windows(eng, name, c, out, out_start, expect, extra_marks=True, extra=()):
     """windows by byte position of the input and of the output: out[out_start[r0] : out_start[r0 + k]] against expect(text of the window, r0, r1)"""
     torch, b = eng.torch, c["b"]
     seen = set()
-    for label, r0 in lt.windows(torch, b.n, b.rec_start, dict(output=out_start), lt.SEED):
+    for label, r0 in lt.windows(torch, b.n, b.rec_start, dict(output=out_start), lt.SEED, extra=extra):
         r1 = r0 + min(lt.KI, b.n)
         w = "%s, window %s (records %d..%d)" % (name, label, r0, r1)
         a, e = int(b.rec_start[r0]), int(b.rec_start[r1])
@@ -323,6 +323,58 @@ def run_format_revcomp(eng, shape="fastq_lf"):
     assert _newlines(torch, out) == 4 * b.n
     seen = _format_windows(eng, name, c, out, out_start, lambda wtext, r0, r1: b"".join(lt.revcomp_plain(wtext)))
     assert {"prefix", "suffix", "random", "input 2^%d" % _lo(), "output 2^%d" % _lo(), "output 2^%d" % _hi()} <= seen, (name, seen)
+    print("large_offsets text %s: %d bytes (%.3f GiB), windows %s" % (name, total, total / 2**30, sorted(seen)))
+
+
+MODE_OPTS = {            # id_mode, id_both, ordinal_base, qual_mode (include/fxg.h)
+    "numeric-ordinal": (1, 1, 10 ** 19 - 2, 2),
+    "ascii-sequence": (2, 1, 0, 1),
+}
+
+
+def run_format_modes(eng, shape, mode):
+    """fxg_fastq_format_opts on the whole block, every record kept through d_len (res null), with the output modes on: the character quality lines
+    go out as numbers under 20-digit ordinal ids on both name lines (7.8 GiB), or every line as characters under sequence ids on both
+    (more than 2^32 bytes too).  d_out holds exactly the closed-form total; out_bytes, the newline and blank counts of the whole output, and windows
+    by output position -- prefix, suffix, 2^31, 2^32, 2^33 where the output reaches it, eight seeded -- against the suite's model of the modes
+    (format_opts_cases.expected) on the generator's records."""
+    import format_opts_cases as F
+    from fastx_toolkit_amd.engine import FxgFormatOpts
+    torch = eng.torch
+    c = block(eng, shape)
+    b = c["b"]
+    id_mode, both, base, qual_mode = MODE_OPTS[mode]
+    name = "%s format, %s" % (shape, mode)
+    sz = torch.zeros(b.n + 1, dtype=torch.int64, device=b.device)
+    blanks = 0
+    for s in range(0, b.n, REC_SLAB):
+        e = min(b.n, s + REC_SLAB)
+        rr = b.range(s, e)
+        sz[s + 1:e + 1] = b.mode_sizes(rr, mode, base)
+        f, (_, minus_one) = b.fields(rr), b.numeric_line(rr)
+        blanks += int((f["L"] - 1).sum()) if mode == "numeric-ordinal" else int((minus_one * f["numeric"]).sum())
+    out_start = torch.cumsum(sz, 0)
+    del sz
+    total = int(out_start[-1])
+    assert total > 1 << _hi(), (name, total)
+    rows_qual = packed_rows(eng, c)[1]
+    ob, out = _canaried(torch, eng, total)
+    nb = C.c_uint64()
+    o = FxgFormatOpts(id_mode, both, base, qual_mode, total, c["lens"].data_ptr())
+    eng._after_torch()
+    eng._check(eng.lib.fxg_fastq_format_opts(eng.ctx, c["text"].data_ptr(), 4, c["ix"].line.data_ptr(), c["ix"].cap_lines, c["ix"].flags.data_ptr(), b.n, None, 0, 0, None, None, None,
+                                             rows_qual.data_ptr(), rows_qual.shape[1], 33, 0, out.data_ptr(), C.byref(nb), C.byref(o)))
+    eng._before_torch()
+    torch.cuda.synchronize()
+    assert nb.value == total, "%s: out_bytes %d, expected %d" % (name, nb.value, total)
+    _guards_intact(ob, total, total, name)
+    step = 1 << 30
+    nl, sp = (sum(int((out[s:s + step] == ch).sum()) for s in range(0, total, step)) for ch in (10, 32))
+    assert nl == 4 * b.n and sp == blanks, "%s: %d newlines and %d blanks in the output, expected %d and %d" % (name, nl, sp, 4 * b.n, blanks)
+    extra = [("output 2^33", 1 << 33, out_start)] if total > 1 << 33 else []
+    expect = lambda wtext, r0, r1: F.expected(wtext, 4, 33, id_mode=id_mode, id_both=bool(both), base=base + r0, qual_mode=qual_mode)
+    seen = _format_windows(eng, name, c, out, out_start, expect, extra=extra)
+    assert {"prefix", "suffix", "random", "input 2^%d" % _lo(), "output 2^%d" % _lo(), "output 2^%d" % _hi()} <= seen and ("output 2^33" in seen) == (total > 1 << 33), (name, seen)
     print("large_offsets text %s: %d bytes (%.3f GiB), windows %s" % (name, total, total / 2**30, sorted(seen)))
 
 
@@ -459,6 +511,8 @@ STEPS = {
     "format-every-record": lambda e, s: run_format_handmade(e, s, True),
     "format-revcomp": run_format_revcomp,
     "format-fasta-out": lambda e, s: run_format_handmade(e, s, False, out_fasta=True),
+    "format-numeric-ordinal": lambda e, s: run_format_modes(e, s, "numeric-ordinal"),
+    "format-ascii-sequence": lambda e, s: run_format_modes(e, s, "ascii-sequence"),
     "weights": run_weights,
     "split-97-bol": lambda e, s: run_split(e, s, 97, False),
     "split-97-eol": lambda e, s: run_split(e, s, 97, True),
@@ -468,7 +522,7 @@ STEPS = {
 # in block order: a shape's text is generated and indexed once
 CASES = [("fastq_lf", "index"), ("fastq_lf", "pack"), ("fastq_lf", "format-handmade"), ("fastq_lf", "format-every-record"), ("fastq_lf", "format-revcomp"),
          ("fastq_lf", "split-97-bol"), ("fastq_lf", "split-97-eol"),
-         ("fastq_mixed", "index"), ("fastq_mixed", "pack"),
+         ("fastq_mixed", "index"), ("fastq_mixed", "pack"), ("fastq_mixed", "format-numeric-ordinal"), ("fastq_mixed", "format-ascii-sequence"),
          ("fasta_short", "index"), ("fasta_short", "pack"), ("fasta_short", "format-fasta-out"), ("fasta_short", "weights"),
          ("fasta_short", "split-97-bol"), ("fasta_short", "split-97-eol"), ("fasta_short", "split-4096-bol"), ("fasta_short", "rejection")]
 
@@ -572,3 +626,61 @@ def test_large_offsets_cli_read_buffer_above_the_block_limit(engine, tmp_path_fa
         assert a[2] == z[2]
     finally:
         shutil.rmtree(work, ignore_errors=True)
+
+
+# ---- ordinal ids over more than 2^24 kept records: the rebuilt rank in the id, in the digit offset and in the total ---------------------------
+ORD_CASES = [(2, "hashed", 0), (2, "hashed", 1), (2, "hashed", 2), (2, "all", 0), (2, "all", 1), (2, "all", 2), (4, "hashed", 1), (4, "hashed", 2)]
+ORD_SLAB = 1 << 20                       # kept records per slab of the whole-output comparison
+
+
+@pytest.mark.parametrize("lpr,keep,base", ORD_CASES, ids=["%s-%s-base%d" % ("fasta" if c[0] == 2 else "fastq-both", c[1], c[2]) for c in ORD_CASES])
+def test_large_offsets_text_ordinal_ranks(engine, lpr, keep, base):
+    """fxg_fastq_format_opts with ordinal ids on lt.ORD_N = 2^24 + 2^23 + 5 four-byte records (eight as FASTQ, the id on both name lines): fifteen
+    in sixteen kept by a hash, or all of them, so the kept count passes 2^24 between two of fxg_text_rank's 2^23 steps; bases 0, 10^8 - 2^24 (nine
+    digits from the rank 2^24 - 1 on) and 10^19 - 2 (twenty digits).  The whole output against the closed form in slabs, out_bytes, and the
+    exact-capacity pair: total - 1 refused with both numbers in the message and nothing written, total accepted.  The scan runs three levels."""
+    from fastx_toolkit_amd.engine import FxgFormatOpts
+    torch = engine.torch
+    _CACHE.clear()
+    torch.cuda.empty_cache()
+    torch.cuda.reset_peak_memory_stats()
+    t0, before, n, both, base = time.time(), engine.scan_recoveries(), lt.ORD_N, lpr == 4, lt.ORD_BASES[base]
+    rec = torch.frombuffer(bytearray(lt.ORD_RECORD[lpr]), dtype=torch.uint8).to(engine.device)
+    text_len = len(lt.ORD_RECORD[lpr]) * n
+    text = torch.full((text_len + 16,), POISON, dtype=torch.uint8, device=engine.device)
+    text[:text_len] = rec.repeat(n)
+    ix, lens, info = engine.fastq_index(text, text_len, cap_records=n + 2, fasta=not both)
+    assert info.records == n and info.irregular == 0 and info.consumed == text_len and info.max_len == 1, (info.records, info.irregular, info.consumed)
+    rows = torch.full((n,), ord("I"), dtype=torch.uint8, device=engine.device)                       # the quality rows at stride 1
+    kmask = lt.ord_keep(torch, torch.arange(n, dtype=torch.int64, device=engine.device)) if keep == "hashed" else torch.ones(n, dtype=torch.bool, device=engine.device)
+    kept = int(kmask.sum())
+    assert kept > (1 << 24) + (1 << 22) and (keep == "all") == (kept == n)
+    res = torch.where(kmask, (1 << 16) | 1, 0).to(torch.int32)
+    total = lt.ord_offset(base, kept, both)
+    ob, out = _canaried(torch, engine, total)
+    nb = C.c_uint64(7)
+
+    def call(cap):
+        o = FxgFormatOpts(1, int(both), base, 0, cap, None)
+        engine._after_torch()
+        rc = engine.lib.fxg_fastq_format_opts(engine.ctx, text.data_ptr(), lpr, ix.line.data_ptr(), ix.cap_lines, ix.flags.data_ptr(), n, res.data_ptr(), 0, 0, None, None, None,
+                                              rows.data_ptr(), 1, 33, 0, out.data_ptr(), C.byref(nb), C.byref(o))
+        engine._before_torch()
+        torch.cuda.synchronize()
+        return rc
+    what = "ordinal ranks %d lines, %s, base %d" % (lpr, keep, base)
+    assert call(total - 1) == E_INVALID and nb.value == 0 and bool((ob == CANARY).all()), what + ": one byte short was not refused untouched"
+    assert engine.lib.fxg_last_error(engine.ctx).decode() == "the formatted block needs %d bytes, d_out takes %d" % (total, total - 1), engine.lib.fxg_last_error(engine.ctx)
+    assert call(total) == 0 and nb.value == total, (what, nb.value, total, engine.lib.fxg_last_error(engine.ctx))
+    _guards_intact(ob, total, total, what)
+    for k0 in range(0, kept, ORD_SLAB):
+        k1 = min(kept, k0 + ORD_SLAB)
+        a, b = lt.ord_offset(base, k0, both), lt.ord_offset(base, k1, both)
+        _same(torch, "%s, kept ranks %d..%d" % (what, k0, k1), out[a:b], lt.ord_text(torch, base, k0, k1, both, device=engine.device), a)
+    torch.cuda.synchronize()
+    assert engine.scan_recoveries() == before and bool((text[text_len:] == POISON).all())
+    peak = torch.cuda.max_memory_allocated()
+    assert peak < MEMORY_LIMIT, "%s: peak of device memory %.1f GB" % (what, peak / 1e9)
+    print("large_offsets text %s: %.1f s, peak %.1f GB" % (what, time.time() - t0, peak / 1e9))
+    del text, out, ob, res, rows, ix, lens
+    torch.cuda.empty_cache()

@@ -604,3 +604,131 @@ def test_format_from_packed_arrays_past_2_24_kept_records():
     bad = np.flatnonzero(got[:, 2] != pk)
     assert bad.size == 0, "kept record %d (of %d differing) has base %r, its packed base is %r" % (bad[0], bad.size, chr(got[bad[0], 2]), chr(pk[bad[0]]))
     assert (pk[1 << 24:] != pk[:k - (1 << 24)]).all()         # (what the wrapped rank would have fetched differs)
+
+
+# ---- 5. ordinal ids: the closed forms, the decimal width sum, and more than 2^24 kept records with the modes on -----------------------------
+@pytest.fixture(scope="module")
+def fmtopts():
+    """the emulation stub with fxg_fastq_format_opts behind it (tests/emu/fmtopts_stub.cpp)"""
+    L = C.CDLL(os.path.join(emu_py.build_fmtopts(), "libfxg.so"))
+    L.fxg_emu_dec_width_sum.restype, L.fxg_emu_dec_width_sum.argtypes = C.c_uint64, [C.c_uint64, C.c_uint64]
+    vp, u64, u32, i32 = C.c_void_p, C.c_uint64, C.c_uint32, C.c_int
+    L.fxg_ctx_create.argtypes = [i32, C.POINTER(vp)]
+    L.fxg_last_error.restype, L.fxg_last_error.argtypes = C.c_char_p, [vp]
+    L.fxg_fastq_format_opts.argtypes = [vp, vp, i32, vp, u64, vp, u64, vp, u32, i32, vp, vp, vp, vp, u32, i32, i32, vp, C.POINTER(u64), C.POINTER(emu_py.FormatOpts)]
+    ctx = vp()
+    assert L.fxg_ctx_create(0, C.byref(ctx)) == 0
+    return L, ctx
+
+
+def test_ordinal_closed_forms_against_plain_python():
+    """large_text.ord_text / ord_offset / dec_width_sum on the first and last 10 000 kept ranks of the 2^24 case, every base, against "%d" in
+    Python and against the suite's model of the formatter (format_opts_cases.expected)"""
+    import format_opts_cases as F
+    kept = int(lt.ord_keep(torch, torch.arange(lt.ORD_N, dtype=torch.int64)).sum())
+    assert (1 << 24) < kept < lt.ORD_N - (1 << 20) and kept > (1 << 24) + (1 << 22)          # fifteen in sixteen: past 2^24, well short of all
+    for base in lt.ORD_BASES:
+        for both in (False, True):
+            for k0, k1 in ((0, 10000), (kept - 10000, kept), ((1 << 24) - 5000, (1 << 24) + 5000), (lt.ORD_N - 10000, lt.ORD_N)):
+                want = b"".join((b"@%d\nA\n+%d\nI\n" % (base + k + 1, base + k + 1)) if both else (b">%d\nA\n" % (base + k + 1)) for k in range(k0, k1))
+                assert bytes(lt.ord_text(torch, base, k0, k1, both).numpy()) == want, (base, both, k0)
+                assert lt.ord_offset(base, k1, both) - lt.ord_offset(base, k0, both) == len(want)
+                assert lt.dec_width_sum(base + 1 + k0, k1 - k0) == sum(len(str(base + 1 + k)) for k in range(k0, k1))
+            lpr = 4 if both else 2
+            assert bytes(lt.ord_text(torch, base, 0, 3000, both).numpy()) == F.expected(lt.ORD_RECORD[lpr] * 3000, lpr, id_mode=1, id_both=both, base=base)
+    line, cap_lines = lt.ord_index(np, 5, 4)
+    text = lt.ORD_RECORD[4] * 5
+    nl = np.flatnonzero(np.frombuffer(text, np.uint8) == 10)
+    assert cap_lines == 21 and np.array_equal(line[1:21], nl + 1) and np.array_equal(line[21:41], nl) and line[0] == 0
+
+
+def test_decimal_width_sum_at_every_power_of_ten(fmtopts):
+    """fxg_dec_width_sum against Python's integers: first at every power of ten, give or take 1, up to 2^64 - 1; counts of 0, 1, 2, 2^24 + 1 and
+    up to the last number a u64 holds (the reference sum itself is held against a plain loop above and here for the small counts)"""
+    L, _ = fmtopts
+    firsts = sorted({10 ** k + d for k in range(20) for d in (-1, 0, 1) if 0 <= 10 ** k + d < 2 ** 64} | {0, 2 ** 64 - 1, 2 ** 64 - 2, 2 ** 63, 2 ** 32 - 1})
+    for a in firsts:
+        for count in (0, 1, 2, 11, (1 << 24) + 1, 2 ** 64 - a):
+            if a + count > 2 ** 64:
+                continue
+            want = lt.dec_width_sum(a, count)
+            if count <= 11:
+                assert want == sum(len(str(a + i)) for i in range(count))
+            assert want < 2 ** 64 or count > 1 << 25
+            if want < 2 ** 64:
+                assert L.fxg_emu_dec_width_sum(a, count) == want, (a, count)
+
+
+def _ordinals_emulated(fmtopts, lpr, keep, base, both):
+    """fxg_fastq_format_opts of the emulation stub over lt.ORD_N records ORD_RECORD[lpr] with ordinal ids: the exact-capacity pair, then (out, kept)"""
+    L, ctx = fmtopts
+    n = lt.ORD_N
+    text = np.tile(np.frombuffer(lt.ORD_RECORD[lpr], np.uint8), n + 4)
+    line, cap_lines = lt.ord_index(np, n, lpr)
+    flags, rows = np.zeros(n, np.uint8), np.full(n, ord("I"), np.uint8)
+    res = np.where(keep, (1 << 16) | 1, 0).astype(np.uint32)
+    kept = int(keep.sum())
+    total = lt.ord_offset(base, kept, both)
+    out = np.full(total + 64, 0xA5, np.uint8)
+    nb = C.c_uint64(7)
+
+    def call(cap):
+        o = emu_py.FormatOpts(1, int(both), base, 0, cap, None)
+        return L.fxg_fastq_format_opts(ctx, text.ctypes.data, lpr, line.ctypes.data, cap_lines, flags.ctypes.data, n, res.ctypes.data, 0, 0, None, None, None, rows.ctypes.data, 1, 33, 0,
+                                       out.ctypes.data, C.byref(nb), C.byref(o))
+    problems = []
+    rc = call(total - 1)
+    if not (rc == -1 and nb.value == 0 and (out == 0xA5).all() and L.fxg_last_error(ctx).decode() == "the formatted block needs %d bytes, d_out takes %d" % (total, total - 1)):
+        problems.append("a d_out of %d bytes, one short of the closed-form total: rc %d, out_bytes %d, \"%s\"" % (total - 1, rc, nb.value, L.fxg_last_error(ctx).decode()))
+        out[:] = 0xA5
+    rc = call(total)
+    if not (rc == 0 and nb.value == total and (out[total:] == 0xA5).all()):
+        problems.append("a d_out of the closed-form total %d: rc %d, out_bytes %d, \"%s\"" % (total, rc, nb.value, L.fxg_last_error(ctx).decode()))
+    return out[:total], kept, problems
+
+
+def test_ordinal_ids_past_2_24_kept_records(fmtopts):
+    """The rank rebuilt at every 2^23-th record feeds the ordinal id and its closed-form digit offset: 2^24 + 2^23 + 5 records, fifteen in sixteen
+    kept, ids that reach nine digits at the rank 2^24 - 1.  out_bytes and the exact-capacity pair (the total is the one thread's sum of
+    copies * D(base + 1, kept) and the scanned offset), and the output at the prefix, around the ranks 2^23, 2^24 - 1 (the wrap of the 24-bit field) and the ranks of the
+    records 2^23, 2^24 and 2^24 + 2^23, and the suffix, against the closed forms."""
+    keep = lt.ord_keep(torch, torch.arange(lt.ORD_N, dtype=torch.int64)).numpy()
+    base = lt.ORD_BASES[1]
+    out, kept, problems = _ordinals_emulated(fmtopts, 2, keep, base, False)
+    rank_of = np.cumsum(keep) - keep
+    marks = [0, 1 << 23, (1 << 24) - 1] + [int(rank_of[r]) for r in (1 << 23, 1 << 24, (1 << 24) + (1 << 23))] + [kept - 1]
+    for m in marks:
+        k0, k1 = max(0, m - 5000), min(kept, m + 5000)
+        a, b = lt.ord_offset(base, k0, False), lt.ord_offset(base, k1, False)
+        want = lt.ord_text(torch, base, k0, k1, False).numpy()
+        if not np.array_equal(out[a:b], want):
+            i = int(np.flatnonzero(out[a:b] != want)[0])
+            problems.append("the ids of the kept ranks %d..%d: from output byte %d on %r, expected %r" % (k0, k1, a + i, bytes(out[a + max(i - 12, 0):a + i + 24]), bytes(want[max(i - 12, 0):i + 24])))
+    if int((out == 10).sum()) != 2 * kept:
+        problems.append("%d newlines for %d kept records" % (int((out == 10).sum()), kept))
+    assert not problems, "\n".join(problems)
+
+
+def test_mode_sizes_against_the_model():
+    """large_text.Block.mode_sizes / numeric_line (the digit sums from the quality hash) on the first and last 10 000 records of a fastq_mixed block,
+    against format_opts_cases.expected on the generated text and against "%d" in plain Python"""
+    import format_opts_cases as F
+    b, rr, text = _small("fastq_mixed", 20000)
+    recs = F.records(text, 4)
+    qbytes, minus_one = b.numeric_line(rr)
+    assert int(b.fields(rr)["numeric"].sum()) > 200
+    for r in list(range(0, 20000, 97)) + list(range(19990, 20000)):
+        vals = F.qual_values(recs[r], 33)
+        assert int(qbytes[r]) == len(b" ".join(b"%d" % v for v in vals)) and int(minus_one[r]) == vals.count(-1), r
+    for mode, (id_mode, both, base, qual_mode) in (("numeric-ordinal", (1, True, 10 ** 19 - 2, 2)), ("ascii-sequence", (2, True, 0, 1))):
+        for r0, r1 in ((0, 10000), (10000, 20000)):
+            wtext = bytes(b.text_of(b.range(r0, r1)).numpy())
+            want = F.expected(wtext, 4, 33, id_mode=id_mode, id_both=both, base=base + r0, qual_mode=qual_mode)
+            sz = b.mode_sizes(b.range(r0, r1), mode, base)
+            assert int(sz.sum()) == len(want), (mode, r0)
+            cut = F.expected(wtext, 4, 33, res=[(1, len(rec[1])) if k < 50 else (0, 0) for k, rec in enumerate(F.records(wtext, 4))], id_mode=id_mode, id_both=both, base=base + r0, qual_mode=qual_mode)
+            assert int(sz[:50].sum()) == len(cut), (mode, r0)
+            if mode == "numeric-ordinal":
+                assert want.count(b" ") == int((b.fields(b.range(r0, r1))["L"] - 1).sum())
+            else:
+                assert want.count(b" ") == int((minus_one * b.fields(rr)["numeric"])[r0:r1].sum())
