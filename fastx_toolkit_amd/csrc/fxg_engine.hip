@@ -5,6 +5,7 @@
 #include "fxg_stats.h"
 #include "fxg_fallback.h"
 #include "fxg_barcode.h"
+#include "fxg_reflow.h"
 
 extern "C" int fxg_abi_version(void) { return FXG_ABI_VERSION; }
 
@@ -43,7 +44,7 @@ extern "C" void fxg_ctx_destroy(fxg_ctx *c)
     (void)hipFree(c->status); (void)hipFree(c->errflag); (void)hipFree(c->counters_scratch);
     (void)hipFree(c->text_ws); (void)hipFree(c->text_state); (void)hipFree(c->fb_blk);
     (void)hipFree(c->hist_buf[0]); (void)hipFree(c->hist_buf[1]); (void)hipFree(c->hist_w); (void)hipFree(c->hist_ws); (void)hipFree(c->stats_ws); (void)hipFree(c->clip_ck);
-    (void)hipFree(c->bc_tab); (void)hipFree(c->bc_ws);
+    (void)hipFree(c->bc_tab); (void)hipFree(c->bc_ws); (void)hipFree(c->rf_ws);
     if (c->ev0) (void)hipEventDestroy(c->ev0);
     if (c->ev1) (void)hipEventDestroy(c->ev1);
     for (int i = 0; i < FXG_KEV_RING; ++i) { if (c->kev0[i]) (void)hipEventDestroy(c->kev0[i]); if (c->kev1[i]) (void)hipEventDestroy(c->kev1[i]); }
@@ -587,6 +588,80 @@ extern "C" int fxg_barcode_split(fxg_ctx *c, const uint8_t *d_text, uint64_t tex
     FXG_HIP(c, hipMemcpyAsync(bin_bytes, a.totals, bins * sizeof(u64), hipMemcpyDeviceToHost, c->stream));
     FXG_HIP(c, hipMemcpyAsync(bin_records, a.totals + bins, bins * sizeof(u64), hipMemcpyDeviceToHost, c->stream));
     FXG_HIP(c, hipStreamSynchronize(c->stream));
+    return FXG_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// fasta_formatter (fxg_reflow.h): line index, classify + segmented scan, sizes + scans, copy
+// ------------------------------------------------------------------------------------------------
+// in-place segmented exclusive scan of (s, kf)[0..n); tmp holds both arrays of every level of block aggregates
+static int fxg_rf_segscan(fxg_ctx *c, u64 *s, u64 *kf, u64 n, u64 *tmp)
+{
+    const u64 nb = (n + FXG_RF_SCAN_BLOCK - 1) / FXG_RF_SCAN_BLOCK;
+    FXG_LAUNCH(c, fxg_kernel_rf_segscan_blocks, (u32)nb, FXG_BLOCK, 0, s, kf, n, tmp, tmp + nb);
+    if (nb > 1) {
+        FXG_TRY(fxg_rf_segscan(c, tmp, tmp + nb, nb, tmp + 2 * nb));
+        FXG_LAUNCH(c, fxg_kernel_rf_segscan_add, (u32)nb, FXG_BLOCK, 0, s, kf, n, (const u64 *)tmp, (const u64 *)(tmp + nb));
+    }
+    return FXG_OK;
+}
+
+// with profiling on, a call leaves three entries in the event ring: classify + segmented scan, sizes + scans, copy
+#define FXG_RF_PHASE_BEGIN(c) do { if ((c)->profiling) FXG_HIP(c, hipEventRecord((c)->kev0[(c)->kev_count % FXG_KEV_RING], (c)->stream)); } while (0)
+#define FXG_RF_PHASE_END(c) do { if ((c)->profiling) { FXG_HIP(c, hipEventRecord((c)->kev1[(c)->kev_count % FXG_KEV_RING], (c)->stream)); (c)->kev_count++; } } while (0)
+
+extern "C" int fxg_fasta_reflow(fxg_ctx *c, const uint8_t *d_text, uint64_t text_len, int at_eof, uint64_t open_bases_in, const fxg_reflow_opts *opts,
+                                uint32_t *d_line, uint64_t cap_lines, uint8_t *d_out, fxg_reflow_info *info)
+{
+    if (!c) return FXG_E_INVALID;
+    FXG_TRY(fxg_rf_check(d_text, text_len, opts, d_line, cap_lines, info, c->err, sizeof c->err));
+    FXG_HIP(c, hipSetDevice(c->device));
+    u64 L = 0;
+    if (text_len) {                                              // the line starts, by the newline kernels of the text path
+        const u64 nseg = (text_len + FXG_TEXT_SEG - 1) / FXG_TEXT_SEG;
+        FXG_TRY(fxg_text_reserve(c, (size_t)(nseg + nseg / 512 + 4096)));
+        const FxgTextState init = fxg_text_state_init();
+        FXG_HIP(c, hipMemcpyAsync(c->text_state, &init, sizeof init, hipMemcpyHostToDevice, c->stream));
+        u64 *seg = c->text_ws, last_count = 0, last_off = 0;
+        FXG_LAUNCH(c, fxg_kernel_nl_count, (u32)nseg, FXG_BLOCK, 0, d_text, (u64)text_len, seg, c->text_state);
+        FXG_HIP(c, hipMemcpyAsync(&last_count, seg + (nseg - 1), sizeof(u64), hipMemcpyDeviceToHost, c->stream));
+        FXG_TRY(fxg_scan_u64(c, seg, nseg, seg + nseg));
+        FXG_HIP(c, hipMemcpyAsync(&last_off, seg + (nseg - 1), sizeof(u64), hipMemcpyDeviceToHost, c->stream));
+        FXG_HIP(c, hipStreamSynchronize(c->stream));
+        L = last_off + last_count;
+        FXG_TRY(fxg_rf_lines_fit(L, cap_lines, c->err, sizeof c->err));
+        FXG_LAUNCH(c, fxg_kernel_nl_scatter, (u32)nseg, FXG_BLOCK, 0, d_text, (u64)text_len, (const u64 *)seg, d_line, d_line + cap_lines, (u64)cap_lines);
+    }
+    const u64 M = L + 2, words = fxg_rf_ws_words(L);
+    FXG_TRY(fxg_ws_grow(c, c->rf_ws, c->rf_ws_cap, (size_t)words, (size_t)(words + words / 4 + 4096)));
+    const FxgRfArgs a = fxg_rf_args(d_text, d_line, L, at_eof, open_bases_in, opts, c->rf_ws, d_out);
+    const u32 grid = (u32)((M + FXG_BLOCK - 1) / FXG_BLOCK);
+    FXG_HIP(c, hipMemsetAsync(a.res, 0, FXG_RF_RES_WORDS * sizeof(u64), c->stream));
+    FXG_RF_PHASE_BEGIN(c);
+    FXG_LAUNCH(c, fxg_kernel_rf_classify, grid, FXG_BLOCK, 0, a);
+    FXG_TRY(fxg_rf_segscan(c, a.seg_s, a.seg_kf, M, fxg_rf_levels(a)));
+    FXG_RF_PHASE_END(c);
+    FXG_RF_PHASE_BEGIN(c);
+    FXG_LAUNCH(c, fxg_kernel_rf_sizes, grid, FXG_BLOCK, 0, a);
+    FXG_TRY(fxg_scan_u64(c, a.size, M, fxg_rf_levels(a)));
+    FXG_TRY(fxg_scan_u64(c, a.pieces, M, fxg_rf_levels(a)));
+    FXG_LAUNCH(c, fxg_kernel_rf_finish, 1, 1, 0, a);
+    FXG_RF_PHASE_END(c);
+    u64 res[FXG_RF_RES_WORDS];
+    FXG_HIP(c, hipMemcpyAsync(res, a.res, sizeof res, hipMemcpyDeviceToHost, c->stream));
+    FXG_HIP(c, hipStreamSynchronize(c->stream));                // nothing may be written before the total is known to fit
+    FXG_TRY(fxg_rf_results(res, L, opts->out_cap, d_out != nullptr, info, c->err, sizeof c->err));
+    const u64 np = res[FXG_RF_RES_PIECES];
+    FXG_RF_PHASE_BEGIN(c);
+    if (res[FXG_RF_RES_OUT_BYTES]) {
+        const u64 hgrid = ((L + 1) * 16 + FXG_BLOCK - 1) / FXG_BLOCK, tgrid = (np * 16 + FXG_BLOCK - 1) / FXG_BLOCK;
+        if (hgrid > 0x7FFFFFFFull || tgrid > 0x7FFFFFFFull) return fxg_fail(c, FXG_E_INVALID, "fxg_fasta_reflow: too many pieces for one launch");
+        FXG_LAUNCH(c, fxg_kernel_rf_copy_heads, (u32)hgrid, FXG_BLOCK, 0, a);
+        if (np) FXG_LAUNCH(c, fxg_kernel_rf_copy_tails, (u32)tgrid, FXG_BLOCK, 0, a, np);
+    }
+    FXG_RF_PHASE_END(c);
+    FXG_HIP(c, hipStreamSynchronize(c->stream));
+    snprintf(c->last_kernel, sizeof c->last_kernel, "fxg_kernel_rf_copy");
     return FXG_OK;
 }
 

@@ -75,6 +75,8 @@ struct fxg_ctx {
     int bc_ready;
     u64 *bc_ws;
     size_t bc_ws_cap;                   // in u64 words
+    u64 *rf_ws;                         // fxg_fasta_reflow: the items' arrays, the scans' levels, the result words (fxg_reflow.h)
+    size_t rf_ws_cap;                   // in u64 words
 };
 
 __attribute__((unused)) static int fxg_fail(fxg_ctx *ctx, int code, const char *fmt, ...)

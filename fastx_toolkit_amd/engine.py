@@ -26,7 +26,7 @@ EXPORTS = [
     "fxg_last_launch_info", "fxg_set_profiling", "fxg_last_kernel_ms", "fxg_profiled_kernel_ms", "fxg_set_clip_history", "fxg_run_quality_stats",
     "fxg_fastq_index", "fxg_fastq_pack", "fxg_fastq_format", "fxg_fastq_format_opts", "fxg_fasta_weights", "fxg_host_register", "fxg_host_unregister",
     "fxg_shard_range", "fxg_epilogue", "fxg_concat_pwrite", "fxg_concat_peer", "fxg_device_count", "fxg_device_numa_node", "fxg_comm_create", "fxg_comm_destroy", "fxg_epilogue_rccl",
-    "fxg_barcode_prepare", "fxg_barcode_split",
+    "fxg_barcode_prepare", "fxg_barcode_split", "fxg_fasta_reflow",
 ]
 
 
@@ -76,6 +76,19 @@ MAX_BARCODE_BINS = 4096       # FXG_MAX_BARCODE_BINS
 class FxgBarcodeSet(C.Structure):
     _fields_ = [("bases", C.c_void_p), ("len", C.c_void_p), ("bin", C.c_void_p), ("entries", C.c_uint32), ("barcode_len", C.c_uint32),
                 ("mismatches", C.c_uint32), ("eol", C.c_uint32), ("bins", C.c_uint32)]
+
+
+class FxgReflowOpts(C.Structure):
+    _fields_ = [("width", C.c_uint32), ("tabular", C.c_uint32), ("keep_empty", C.c_uint32), ("out_cap", C.c_uint64)]
+
+
+class FxgReflowInfo(C.Structure):
+    _fields_ = [("lines", C.c_uint64), ("headers", C.c_uint64), ("consumed", C.c_uint64), ("out_bytes", C.c_uint64), ("open_bases", C.c_uint64)]
+
+
+def reflow_bound(text_len):
+    """Bytes a reflowed block can come to: width 1 doubles the bases, and the end of input may close a record."""
+    return 2 * text_len + 2
 
 
 class FxgOut(C.Structure):
@@ -166,6 +179,8 @@ def load_library(path=None):
     L.fxg_epilogue_rccl.argtypes = [vp, vp, vp, vp, C.POINTER(u64), C.POINTER(u64), vp]
     L.fxg_barcode_prepare.argtypes = [vp, C.POINTER(FxgBarcodeSet)]
     L.fxg_barcode_split.argtypes = [vp, vp, u64, i32, vp, u64, u64, vp, vp, C.POINTER(u64), C.POINTER(u64)]
+    if hasattr(L, "fxg_fasta_reflow"):       # (the CPU tier's look-alike libraries predate the entry; the product library always has it, tests/test_abi.py)
+        L.fxg_fasta_reflow.argtypes = [vp, vp, u64, i32, u64, C.POINTER(FxgReflowOpts), vp, u64, vp, C.POINTER(FxgReflowInfo)]
     L.fxg_set_profiling.argtypes = [vp, i32]
     L.fxg_set_clip_history.argtypes = [vp, i32]
     L.fxg_run_quality_stats.argtypes = [vp, C.POINTER(FxgBatch), vp, C.c_uint32]
@@ -523,6 +538,26 @@ class Engine:
         self._check(self.lib.fxg_barcode_split(self.ctx, d_text.data_ptr(), text_len, ix.lpr, ix.line.data_ptr(), ix.cap_lines, n,
                                                rb.data_ptr() if rb is not None else None, out.data_ptr(), bb, br))
         return out[:nbytes], np.array(list(bb), dtype=np.uint64), np.array(list(br), dtype=np.uint64), (rb[:n] if rb is not None else None)
+
+    def fasta_reflow(self, d_text, text_len, at_eof=True, open_bases_in=0, width=0, tabular=False, keep_empty=False, out=None, out_cap=None,
+                     line=None, cap_lines=None):
+        """fasta_formatter on one block of text (text_upload; fxg_fasta_reflow in include/fxg.h).  Returns (out, info): out is a view of
+        exactly the bytes written, info.consumed / info.open_bases chain the next block.  out / out_cap and line / cap_lines: the caller's
+        own arrays (out_cap may be smaller than out to have a block refused); by default sized for any block of text_len bytes."""
+        if not hasattr(self.lib, "fxg_fasta_reflow"):
+            raise FxgError("this libfxg.so has no fxg_fasta_reflow")
+        if cap_lines is None:
+            cap_lines = text_len + 2
+        if line is None:
+            line = self.torch.empty(2 * cap_lines, dtype=self.torch.int32, device=self.device)
+        if out is None:
+            out = self.torch.empty(max(reflow_bound(text_len), 16), dtype=self.torch.uint8, device=self.device)
+        o = FxgReflowOpts(width, int(bool(tabular)), int(bool(keep_empty)), out.numel() if out_cap is None else out_cap)
+        info = FxgReflowInfo()
+        self._after_torch()
+        self._check(self.lib.fxg_fasta_reflow(self.ctx, d_text.data_ptr(), text_len, int(bool(at_eof)), open_bases_in, C.byref(o), line.data_ptr(), cap_lines,
+                                              out.data_ptr(), C.byref(info)))
+        return out[:info.out_bytes], info
 
     def read_counters(self, d_counters):
         host = (C.c_uint64 * NCOUNTERS)()

@@ -36,7 +36,7 @@
 extern "C" {
 #endif
 
-#define FXG_ABI_VERSION 5
+#define FXG_ABI_VERSION 6
 
 /* ---- error codes ---- */
 #define FXG_OK            0
@@ -184,6 +184,9 @@ typedef struct fxg_out {
  *   barcode split (below)    d_text: read as for the text path; d_line: the line starts ls[0 .. lines_per_record * records] (first half only);
  *                            d_rec_bin: write records uint16; d_out: write exactly ls[lines_per_record * records] - ls[0] bytes (the records
  *                            themselves), never a byte past them.
+ *   fasta reflow (below)     d_text: read as for the text path (text_len + 16 bytes); d_line: 2 * cap_lines uint32 as for the text path, of which
+ *                            the line starts ls[0 .. lines] are read back; d_out: write exactly info->out_bytes bytes, never a byte past them,
+ *                            and none at all when the request is refused.
  * tests/test_emu_bounds.py runs the kernels' bodies with every array against a guard page at these ends; tests/test_gpu_bounds.py surrounds every
  * array with poison (inputs) and canaries (outputs) on the device. */
 
@@ -338,6 +341,38 @@ int  fxg_barcode_prepare(fxg_ctx *ctx, const fxg_barcode_set *set);
  * (host, bins entries each) say how many.  d_rec_bin (optional): the bin of every record.  Synchronises. */
 int  fxg_barcode_split(fxg_ctx *ctx, const uint8_t *d_text, uint64_t text_len, int lines_per_record, const uint32_t *d_line, uint64_t cap_lines,
                        uint64_t records, uint16_t *d_rec_bin, uint8_t *d_out, uint64_t *bin_bytes, uint64_t *bin_records);
+/* fasta_formatter (reference src/fasta_formatter/fasta_formatter.cpp:136-201, sequence_writers.h:31-109): multi-line FASTA reflowed on the
+ * device.  The block is split at '\n'; only complete lines count.  Lines of length 0 are skipped, a line whose first byte is '>' starts a
+ * record and is its id line H, every other line is appended to the open record's bases B as its bytes are (CR, NUL, lower case and blanks
+ * are kept).  A record goes out as "H\n B\n" (width 0), as "H\n" and B in lines of `width` bytes (a shorter last line, never an empty one),
+ * or as "H[1:]\t B\n" (tabular, which wins over width); a record without bases as "H\n" / "H[1:]\n" with keep_empty, not at all without.
+ * Blocks chain through one number: open_bases_in is how many bases of the record open at the block's start are already written (0: no record
+ * is open), info->open_bases is that number for the next block, which starts at info->consumed.  What closes a record -- the '\n' after
+ * its last bases if one is due, or the id line of a record without bases -- is written when the next header line or the end of input
+ * (at_eof) comes, so a call with text_len == 0, at_eof != 0 and open_bases_in > 0 writes that newline.  consumed ends after the last complete
+ * line, except that, not at the end of input, the block's last header line is not consumed while no non-empty sequence line follows it: it
+ * closes the record before it in this block and is read again with the next one.  (So consumed == 0 before the end of input means: the block
+ * must grow.)  A non-empty sequence line with no header before it in the block while open_bases_in == 0 is refused; the host keeps such
+ * input (sequence lines before the first header) away from the device.  The block's output size is known before anything is written: more
+ * than out_cap bytes is refused (FXG_E_INVALID, the message says how many) with d_out untouched; 2 * text_len + 2 always suffices (width 1
+ * doubles the bases).  d_text, text_len, d_line, cap_lines: as for the text path, cap_lines >= lines + 1 (refused otherwise, the message
+ * says how many), every offset inside a block is 32-bit (text_len <= 0xFFFFFFF0), output offsets are 64-bit.  Synchronises.  With profiling
+ * on, a call records three intervals: classify + segmented scan, sizes + scans, copy. */
+typedef struct fxg_reflow_opts {
+    uint32_t width;        /* -w: 0 = one line per record */
+    uint32_t tabular;      /* -t */
+    uint32_t keep_empty;   /* -e */
+    uint64_t out_cap;      /* bytes d_out can take */
+} fxg_reflow_opts;
+typedef struct fxg_reflow_info {
+    uint64_t lines;        /* complete lines in the block */
+    uint64_t headers;      /* of which header lines */
+    uint64_t consumed;     /* the next block starts there */
+    uint64_t out_bytes;    /* written to d_out */
+    uint64_t open_bases;   /* open_bases_in of the next block */
+} fxg_reflow_info;
+int  fxg_fasta_reflow(fxg_ctx *ctx, const uint8_t *d_text, uint64_t text_len, int at_eof, uint64_t open_bases_in, const fxg_reflow_opts *opts,
+                      uint32_t *d_line, uint64_t cap_lines, uint8_t *d_out, fxg_reflow_info *info);
 int  fxg_host_register(fxg_ctx *ctx, void *ptr, size_t bytes);     /* page-lock an existing host buffer for async copies */
 int  fxg_host_unregister(fxg_ctx *ctx, void *ptr);
 
