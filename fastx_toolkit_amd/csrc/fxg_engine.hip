@@ -23,11 +23,7 @@ extern "C" int fxg_ctx_create(int device_id, fxg_ctx **out)
         hipStreamCreateWithFlags(&c->own_stream, hipStreamNonBlocking) != hipSuccess) { fxg_ctx_destroy(c); return FXG_E_HIP; }
     c->cus = prop.multiProcessorCount;
     c->stream = c->own_stream;
-    { const char *e = getenv("FXG_BLOCKS_PER_CU"); c->env_blocks_per_cu = (e && atoi(e) > 0 && atoi(e) <= 16) ? atoi(e) : 0; }
-    { const char *e = getenv("FXG_WORKERS"); c->env_workers = (e && atoi(e) > 0) ? atoi(e) : 0; }
-    { const char *e = getenv("FXG_NSCAN"); c->env_nscan = (e && atoi(e) > 0 && atoi(e) <= 64) ? atoi(e) : 0; }
-    { const char *e = getenv("FXG_TEST_SCAN_TIMEOUT"); c->test_force_timeout = (e && atoi(e) > 0) ? 1 : 0; }
-    { const char *e = getenv("FXG_TICKET_GROUPS"); c->env_ticket_groups = (e && atoi(e) > 0 && atoi(e) <= FXG_TICKET_GROUPS) ? atoi(e) : 0; }
+    c->knobs = fxg_knobs_read(FXG_KNOBS_CONTEXT);
     if (hipEventCreate(&c->ev0) != hipSuccess || hipEventCreate(&c->ev1) != hipSuccess ||
         hipMalloc((void **)&c->errflag, (FXG_CTRL_WORDS + FXG_TICKET_GROUPS * FXG_TICKET_STRIDE) * sizeof(u32)) != hipSuccess ||
         hipMalloc((void **)&c->counters_scratch, FXG_NCOUNTERS * sizeof(u64)) != hipSuccess) { fxg_ctx_destroy(c); return FXG_E_HIP; }
@@ -188,7 +184,7 @@ extern "C" int fxg_run_pipeline(fxg_ctx *c, const fxg_batch *in, const fxg_param
     if (!c || !in || !p || !out) return FXG_E_INVALID;
     FxgPlan pl;
     bool hist; u32 estride;
-    FXG_TRY(fxg_plan_request(in, p, out, c->hist_on != 0, c->hist_wcap, &pl, &hist, &estride, c->err, sizeof c->err));
+    FXG_TRY(fxg_plan_request(in, p, out, c->hist_on != 0, c->hist_wcap, &pl, &hist, &estride, c->err, sizeof c->err, fxg_knobs_read(FXG_KNOBS_REQUEST)));
     if (in->n == 0) {
         if (out->counters) FXG_HIP(c, hipMemsetAsync(out->counters, 0, FXG_NCOUNTERS * sizeof(u64), c->stream));
         return FXG_OK;
@@ -213,36 +209,21 @@ static int fxg_launch_clip(fxg_ctx *c, FxgPlan &pl, u64 *ctr)
     return fxg_fail(c, FXG_E_INVALID, "no clip instance %d", pl.amax);
 }
 
-// the launch of a planned pass: which instance of which kernel family
+// the launch of a planned pass: the instance the plan names (fxg_instances.h)
 static int fxg_launch_plan(fxg_ctx *c, FxgPlan &pl, u64 *ctr)
 {
-    if (pl.rows_nw) {       // rows of 80..152 bytes through the quality stages: one lane per read, rows in registers (fxg_rows.h)
-        if (pl.rows_h == 2) {     // rows of 153..304 bytes: two lanes per read
-            if (pl.rows_nw == 26) return fxg_launch_tiles(c, fxg_kernel_rows<26, 2>, "fxg_kernel_rows<26,2> qtrim+qfilter", pl.ka, pl.lds, ctr, 64u, true);
-            return fxg_launch_tiles(c, fxg_kernel_rows<38, 2>, "fxg_kernel_rows<38,2> qtrim+qfilter", pl.ka, pl.lds, ctr, 64u, true);
-        }
-        switch (pl.rows_nw) {
-        case 10: return fxg_launch_tiles(c, fxg_kernel_rows_multi<10, 4>, "fxg_kernel_rows_multi<10,4> qtrim+qfilter", pl.ka, pl.lds, ctr, 64u, true);      // rows of 28..40 bytes, four reads per lane
-        case 14: return fxg_launch_tiles(c, fxg_kernel_rows_multi<14, 3>, "fxg_kernel_rows_multi<14,3> qtrim+qfilter", pl.ka, pl.lds, ctr, 64u, true);      // 41..56 bytes, three
-        case 20: return fxg_launch_tiles(c, fxg_kernel_rows_multi<20, 2>, "fxg_kernel_rows_multi<20,2> qtrim+qfilter", pl.ka, pl.lds, ctr, 64u, true);      // 57..79 bytes, two
-        case 26: return fxg_launch_tiles(c, fxg_kernel_rows<26>, "fxg_kernel_rows<26> qtrim+qfilter", pl.ka, pl.lds, ctr, 64u, true);
-        default: return fxg_launch_tiles(c, fxg_kernel_rows<38>, "fxg_kernel_rows<38> qtrim+qfilter", pl.ka, pl.lds, ctr, 64u, true);
-        }
+    switch (pl.inst) {
+#define FXG_INST_LAUNCH(ID, KERNEL, NAME, ROWS, AMAX, REV, MODE, NW, H, R) case FXG_INST_##ID: return fxg_launch_tiles(c, KERNEL, pl, ctr, ROWS);
+    FXG_INSTANCES(FXG_INST_LAUNCH)
+#undef FXG_INST_LAUNCH
+    default: return fxg_launch_clip(c, pl, ctr);
     }
-    if (pl.group_a) {
-        if (pl.amax == 0) return fxg_launch_tiles(c, fxg_kernel_tiles<0, 0>, "fxg_kernel_tiles<0,0> qtrim+qfilter", pl.ka, pl.lds, ctr);
-        return fxg_launch_clip(c, pl, ctr);
-    }
-    if (pl.mask) return fxg_launch_tiles(c, fxg_kernel_tiles<0, 3>, "fxg_kernel_tiles<0,3> mask", pl.ka, pl.lds, ctr);
-    if (pl.artifacts) return fxg_launch_tiles(c, fxg_kernel_tiles<0, 4>, "fxg_kernel_tiles<0,4> base census", pl.ka, pl.lds, ctr);
-    if (pl.rev && pl.ka.rev_dw) return fxg_launch_tiles(c, fxg_kernel_tiles<0, 5>, "fxg_kernel_tiles<0,5> revcomp[+ftrim], dword-aligned windows", pl.ka, pl.lds, ctr);
-    if (pl.rev) return fxg_launch_tiles(c, fxg_kernel_tiles<0, 2>, "fxg_kernel_tiles<0,2> revcomp[+ftrim]", pl.ka, pl.lds, ctr);
-    return fxg_launch_tiles(c, fxg_kernel_tiles<0, 1>, "fxg_kernel_tiles<0,1> ftrim", pl.ka, pl.lds, ctr);
 }
 
 extern "C" int fxg_run_quality_stats(fxg_ctx *c, const fxg_batch *in, uint64_t *d_hist, uint32_t hist_cols)
 {
     if (!c) return FXG_E_INVALID;
+    const FxgKnobs kn = fxg_knobs_read(FXG_KNOBS_REQUEST);
     FXG_TRY(fxg_stats_check(in, d_hist, hist_cols, c->err, sizeof c->err));
     if (in->n == 0) return FXG_OK;
     FXG_HIP(c, hipSetDevice(c->device));
@@ -253,25 +234,22 @@ extern "C" int fxg_run_quality_stats(fxg_ctx *c, const fxg_batch *in, uint64_t *
     const size_t need = (size_t)a.nwg * FXG_QS_PART_WORDS;
     FXG_TRY(fxg_ws_grow(c, c->stats_ws, c->stats_ws_cap, need, need));
     a.partial = c->stats_ws;
-    a.round_robin = 1u;
-    if (const char *e = getenv("FXG_QS_ROUND_ROBIN")) a.round_robin = (u32)strtoul(e, nullptr, 0);      // measurement knob (csrc/fxg_stats.h: FxgStatsArgs::round_robin): 0 = one static slice per workgroup, tested loads; 3 = the row-strip form where the piece form would run
+    a.round_robin = kn.qs_round_robin;      // FXG_QS_ROUND_ROBIN (measurement knob)
     const u32 lds = FXG_QS_LDS_WORDS * sizeof(u32);
     FXG_HIP(c, hipFuncSetAttribute((const void *)fxg_kernel_quality_stats, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     FXG_HIP(c, hipFuncSetAttribute((const void *)fxg_kernel_quality_stats_odd, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     const u32 nstrips = (in->stride + FXG_QS_STRIP - 1) / FXG_QS_STRIP;
     for (u32 s0 = 0; s0 < nstrips; s0 += FXG_QS_WAVES) {       // one pass per block of 160 columns (one pass for reads up to 160)
         a.strip0 = s0;
-        const bool timed = c->profiling && s0 == 0;
-        if (timed) FXG_HIP(c, hipEventRecord(c->kev0[c->kev_count % FXG_KEV_RING], c->stream));
+        if (s0 == 0) FXG_PROFILE_BEGIN(c);
         u32 pr = 0, pp = 0;
         // dense batches of odd length 17 .. 159: the piece form that keeps LDS block and counter half per byte, a kernel (and a register allocation) of its own
         if (a.round_robin == 1u && (a.fixed_len & 1u) && fxg_stats_piece_plan(a, &pr, &pp)) FXG_LAUNCH(c, fxg_kernel_quality_stats_odd, a.nwg, FXG_QS_TBLOCK, lds, a);
         else FXG_LAUNCH(c, fxg_kernel_quality_stats, a.nwg, FXG_QS_TBLOCK, lds, a);
-        if (timed) { FXG_HIP(c, hipEventRecord(c->kev1[c->kev_count % FXG_KEV_RING], c->stream)); c->kev_count++; }
+        if (s0 == 0) FXG_PROFILE_END(c);
         FXG_LAUNCH(c, fxg_kernel_quality_stats_fold, (FXG_QS_PART_WORDS + FXG_QS_FOLD_E - 1) / FXG_QS_FOLD_E, 256, 0, a);
     }
-    snprintf(c->last_kernel, sizeof c->last_kernel, "fxg_kernel_quality_stats");
-    c->last_grid = a.nwg; c->last_block = FXG_QS_TBLOCK; c->last_lds = lds; c->last_tile = 64u * FXG_QS_UNROLL;
+    fxg_note_launch(c, "fxg_kernel_quality_stats", a.nwg, FXG_QS_TBLOCK, lds, 64u * FXG_QS_UNROLL);
     return FXG_OK;
 }
 
@@ -330,7 +308,7 @@ static int fxg_redo_without_scanner(fxg_ctx *c)
     fxg_out o2 = c->fb_req.out;
     o2.out_bases = o2.out_qual = nullptr; o2.out_len = nullptr; o2.kept_index = nullptr; o2.out_off = nullptr;
     FxgPlan pl;
-    FXG_TRY(fxg_make_plan(&c->fb_req.in, &c->fb_req.p, &o2, &pl, c->err, sizeof c->err, c->fb_req.hist ? c->fb_req.estride : 0u));
+    FXG_TRY(fxg_make_plan(&c->fb_req.in, &c->fb_req.p, &o2, &pl, c->err, sizeof c->err, c->fb_req.hist ? c->fb_req.estride : 0u, fxg_knobs_read(FXG_KNOBS_REQUEST)));
     if (c->fb_req.hist) fxg_plan_clip_from(&pl, failed.clip_src, failed.clip_stride, failed.clip_total, failed.wlen);
     FXG_HIP(c, hipSetDevice(c->device));
     FXG_TRY(fxg_launch_plan(c, pl, counters));
@@ -358,10 +336,11 @@ extern "C" int fxg_scan_recoveries(const fxg_ctx *c) { return c ? c->recoveries 
 extern "C" int fxg_read_counters(fxg_ctx *c, const uint64_t *d_counters, uint64_t host[FXG_NCOUNTERS])
 {
     if (!c || !host) return FXG_E_INVALID;
+    const FxgKnobs kn = fxg_knobs_read(FXG_KNOBS_REQUEST);
     const u64 *src = d_counters ? (const u64 *)d_counters : c->counters_scratch;
     FXG_HIP(c, hipMemcpyAsync(host, src, FXG_NCOUNTERS * sizeof(u64), hipMemcpyDeviceToHost, c->stream));
     FXG_HIP(c, hipStreamSynchronize(c->stream));
-    if ((host[FXG_C_ERRORS] & FXG_DEV_ERR_SCAN_TIMEOUT) && c->fb.valid && c->fb_req.valid && src == (c->fb.counters ? c->fb.counters : c->counters_scratch) && !getenv("FXG_NO_SCAN_FALLBACK")) {
+    if ((host[FXG_C_ERRORS] & FXG_DEV_ERR_SCAN_TIMEOUT) && c->fb.valid && c->fb_req.valid && src == (c->fb.counters ? c->fb.counters : c->counters_scratch) && !kn.no_scan_fallback) {
         // the launch these counters belong to gave up waiting (its workgroups were not being scheduled): the same work again without anything that waits
         c->fb.valid = 0; c->fb_req.valid = 0;
         FXG_TRY(fxg_redo_without_scanner(c));
@@ -413,6 +392,31 @@ static int fxg_scan_u64(fxg_ctx *c, u64 *data, u64 n, u64 *tmp)
     return FXG_OK;
 }
 
+// The line index of a block of text (text_len > 0): the newline census per segment, its scan, the line starts and ends scattered into d_ls / d_le.  The one wait
+// for *lines comes behind the scatter, or (fit_first: fxg_fasta_reflow) ahead of it, and nothing is scattered unless the lines fit.
+static int fxg_line_index(fxg_ctx *c, const uint8_t *d_text, u64 text_len, u32 *d_ls, u32 *d_le, u64 cap_lines, bool fit_first, u64 *lines)
+{
+    const u64 nseg = (text_len + FXG_TEXT_SEG - 1) / FXG_TEXT_SEG;
+    FXG_TRY(fxg_text_reserve(c, (size_t)(nseg + nseg / 512 + 4096)));
+    const FxgTextState init = fxg_text_state_init();
+    FXG_HIP(c, hipMemcpyAsync(c->text_state, &init, sizeof init, hipMemcpyHostToDevice, c->stream));
+    u64 *seg = c->text_ws;
+    FXG_LAUNCH(c, fxg_kernel_nl_count, (u32)nseg, FXG_BLOCK, 0, d_text, text_len, seg, c->text_state);
+    // total newlines = last exclusive prefix + last count: keep the last count before the scan overwrites it
+    u64 last_count = 0, last_off = 0;
+    FXG_HIP(c, hipMemcpyAsync(&last_count, seg + (nseg - 1), sizeof(u64), hipMemcpyDeviceToHost, c->stream));
+    FXG_TRY(fxg_scan_u64(c, seg, nseg, seg + nseg));
+    FXG_HIP(c, hipMemcpyAsync(&last_off, seg + (nseg - 1), sizeof(u64), hipMemcpyDeviceToHost, c->stream));
+    if (fit_first) {
+        FXG_HIP(c, hipStreamSynchronize(c->stream));
+        FXG_TRY(fxg_rf_lines_fit(last_off + last_count, cap_lines, c->err, sizeof c->err));
+    }
+    FXG_LAUNCH(c, fxg_kernel_nl_scatter, (u32)nseg, FXG_BLOCK, 0, d_text, text_len, (const u64 *)seg, d_ls, d_le, cap_lines);
+    if (!fit_first) FXG_HIP(c, hipStreamSynchronize(c->stream));
+    *lines = last_off + last_count;
+    return FXG_OK;
+}
+
 extern "C" int fxg_fastq_index(fxg_ctx *c, const uint8_t *d_text, uint64_t text_len, int at_eof, int lines_per_record, uint32_t *d_line,
                                uint64_t cap_lines, uint16_t *d_len, uint8_t *d_flags, fxg_text_info *info)
 {
@@ -421,21 +425,10 @@ extern "C" int fxg_fastq_index(fxg_ctx *c, const uint8_t *d_text, uint64_t text_
     if (text_len == 0) return FXG_OK;
     FXG_HIP(c, hipSetDevice(c->device));
     const u64 lpr = (u64)lines_per_record;
-    const u64 nseg = (text_len + FXG_TEXT_SEG - 1) / FXG_TEXT_SEG;
-    FXG_TRY(fxg_text_reserve(c, (size_t)(nseg + nseg / 512 + 4096)));
     u32 *d_ls = d_line, *d_le = d_line + cap_lines;
-    const FxgTextState init = fxg_text_state_init();
-    FXG_HIP(c, hipMemcpyAsync(c->text_state, &init, sizeof init, hipMemcpyHostToDevice, c->stream));
-    u64 *seg = c->text_ws;
-    FXG_LAUNCH(c, fxg_kernel_nl_count, (u32)nseg, FXG_BLOCK, 0, d_text, (u64)text_len, seg, c->text_state);
-    // total newlines = last exclusive prefix + last count: keep the last count before the scan overwrites it
-    u64 last_count = 0, last_off = 0;
-    FXG_HIP(c, hipMemcpyAsync(&last_count, seg + (nseg - 1), sizeof(u64), hipMemcpyDeviceToHost, c->stream));
-    FXG_TRY(fxg_scan_u64(c, seg, nseg, seg + nseg));
-    FXG_HIP(c, hipMemcpyAsync(&last_off, seg + (nseg - 1), sizeof(u64), hipMemcpyDeviceToHost, c->stream));
-    FXG_LAUNCH(c, fxg_kernel_nl_scatter, (u32)nseg, FXG_BLOCK, 0, d_text, (u64)text_len, (const u64 *)seg, d_ls, d_le, (u64)cap_lines);
-    FXG_HIP(c, hipStreamSynchronize(c->stream));
-    const u64 lines = last_off + last_count, n = fxg_text_records(lines, lpr, cap_lines);
+    u64 lines = 0;
+    FXG_TRY(fxg_line_index(c, d_text, text_len, d_ls, d_le, cap_lines, false, &lines));
+    const u64 n = fxg_text_records(lines, lpr, cap_lines);
     if (n == 0) { fxg_text_info_fill(info, nullptr, lines, lpr, 0, 0, text_len, at_eof); return FXG_OK; }
     const u32 grid = (u32)((n + FXG_BLOCK - 1) / FXG_BLOCK);
     if (lines_per_record == 4) FXG_LAUNCH(c, fxg_kernel_text_records<4>, grid, FXG_BLOCK, 0, d_text, (const u32 *)d_ls, d_le, n, d_len, d_flags, c->text_state);
@@ -607,9 +600,6 @@ static int fxg_rf_segscan(fxg_ctx *c, u64 *s, u64 *kf, u64 n, u64 *tmp)
 }
 
 // with profiling on, a call leaves three entries in the event ring: classify + segmented scan, sizes + scans, copy
-#define FXG_RF_PHASE_BEGIN(c) do { if ((c)->profiling) FXG_HIP(c, hipEventRecord((c)->kev0[(c)->kev_count % FXG_KEV_RING], (c)->stream)); } while (0)
-#define FXG_RF_PHASE_END(c) do { if ((c)->profiling) { FXG_HIP(c, hipEventRecord((c)->kev1[(c)->kev_count % FXG_KEV_RING], (c)->stream)); (c)->kev_count++; } } while (0)
-
 extern "C" int fxg_fasta_reflow(fxg_ctx *c, const uint8_t *d_text, uint64_t text_len, int at_eof, uint64_t open_bases_in, const fxg_reflow_opts *opts,
                                 uint32_t *d_line, uint64_t cap_lines, uint8_t *d_out, fxg_reflow_info *info)
 {
@@ -617,51 +607,37 @@ extern "C" int fxg_fasta_reflow(fxg_ctx *c, const uint8_t *d_text, uint64_t text
     FXG_TRY(fxg_rf_check(d_text, text_len, opts, d_line, cap_lines, info, c->err, sizeof c->err));
     FXG_HIP(c, hipSetDevice(c->device));
     u64 L = 0;
-    if (text_len) {                                              // the line starts, by the newline kernels of the text path
-        const u64 nseg = (text_len + FXG_TEXT_SEG - 1) / FXG_TEXT_SEG;
-        FXG_TRY(fxg_text_reserve(c, (size_t)(nseg + nseg / 512 + 4096)));
-        const FxgTextState init = fxg_text_state_init();
-        FXG_HIP(c, hipMemcpyAsync(c->text_state, &init, sizeof init, hipMemcpyHostToDevice, c->stream));
-        u64 *seg = c->text_ws, last_count = 0, last_off = 0;
-        FXG_LAUNCH(c, fxg_kernel_nl_count, (u32)nseg, FXG_BLOCK, 0, d_text, (u64)text_len, seg, c->text_state);
-        FXG_HIP(c, hipMemcpyAsync(&last_count, seg + (nseg - 1), sizeof(u64), hipMemcpyDeviceToHost, c->stream));
-        FXG_TRY(fxg_scan_u64(c, seg, nseg, seg + nseg));
-        FXG_HIP(c, hipMemcpyAsync(&last_off, seg + (nseg - 1), sizeof(u64), hipMemcpyDeviceToHost, c->stream));
-        FXG_HIP(c, hipStreamSynchronize(c->stream));
-        L = last_off + last_count;
-        FXG_TRY(fxg_rf_lines_fit(L, cap_lines, c->err, sizeof c->err));
-        FXG_LAUNCH(c, fxg_kernel_nl_scatter, (u32)nseg, FXG_BLOCK, 0, d_text, (u64)text_len, (const u64 *)seg, d_line, d_line + cap_lines, (u64)cap_lines);
-    }
+    if (text_len) FXG_TRY(fxg_line_index(c, d_text, text_len, d_line, d_line + cap_lines, cap_lines, true, &L));      // the line starts, by the newline kernels of the text path
     const u64 M = L + 2, words = fxg_rf_ws_words(L);
     FXG_TRY(fxg_ws_grow(c, c->rf_ws, c->rf_ws_cap, (size_t)words, (size_t)(words + words / 4 + 4096)));
     const FxgRfArgs a = fxg_rf_args(d_text, d_line, L, at_eof, open_bases_in, opts, c->rf_ws, d_out);
     const u32 grid = (u32)((M + FXG_BLOCK - 1) / FXG_BLOCK);
     FXG_HIP(c, hipMemsetAsync(a.res, 0, FXG_RF_RES_WORDS * sizeof(u64), c->stream));
-    FXG_RF_PHASE_BEGIN(c);
+    FXG_PROFILE_BEGIN(c);
     FXG_LAUNCH(c, fxg_kernel_rf_classify, grid, FXG_BLOCK, 0, a);
     FXG_TRY(fxg_rf_segscan(c, a.seg_s, a.seg_kf, M, fxg_rf_levels(a)));
-    FXG_RF_PHASE_END(c);
-    FXG_RF_PHASE_BEGIN(c);
+    FXG_PROFILE_END(c);
+    FXG_PROFILE_BEGIN(c);
     FXG_LAUNCH(c, fxg_kernel_rf_sizes, grid, FXG_BLOCK, 0, a);
     FXG_TRY(fxg_scan_u64(c, a.size, M, fxg_rf_levels(a)));
     FXG_TRY(fxg_scan_u64(c, a.pieces, M, fxg_rf_levels(a)));
     FXG_LAUNCH(c, fxg_kernel_rf_finish, 1, 1, 0, a);
-    FXG_RF_PHASE_END(c);
+    FXG_PROFILE_END(c);
     u64 res[FXG_RF_RES_WORDS];
     FXG_HIP(c, hipMemcpyAsync(res, a.res, sizeof res, hipMemcpyDeviceToHost, c->stream));
     FXG_HIP(c, hipStreamSynchronize(c->stream));                // nothing may be written before the total is known to fit
     FXG_TRY(fxg_rf_results(res, L, opts->out_cap, d_out != nullptr, info, c->err, sizeof c->err));
     const u64 np = res[FXG_RF_RES_PIECES];
-    FXG_RF_PHASE_BEGIN(c);
+    FXG_PROFILE_BEGIN(c);
     if (res[FXG_RF_RES_OUT_BYTES]) {
         const u64 hgrid = ((L + 1) * 16 + FXG_BLOCK - 1) / FXG_BLOCK, tgrid = (np * 16 + FXG_BLOCK - 1) / FXG_BLOCK;
         if (hgrid > 0x7FFFFFFFull || tgrid > 0x7FFFFFFFull) return fxg_fail(c, FXG_E_INVALID, "fxg_fasta_reflow: too many pieces for one launch");
         FXG_LAUNCH(c, fxg_kernel_rf_copy_heads, (u32)hgrid, FXG_BLOCK, 0, a);
         if (np) FXG_LAUNCH(c, fxg_kernel_rf_copy_tails, (u32)tgrid, FXG_BLOCK, 0, a, np);
     }
-    FXG_RF_PHASE_END(c);
+    FXG_PROFILE_END(c);
     FXG_HIP(c, hipStreamSynchronize(c->stream));
-    snprintf(c->last_kernel, sizeof c->last_kernel, "fxg_kernel_rf_copy");
+    fxg_note_launch(c, "fxg_kernel_rf_copy", c->last_grid, c->last_block, c->last_lds, c->last_tile);      // (several kernels: no one geometry to report, the last one stays)
     return FXG_OK;
 }
 

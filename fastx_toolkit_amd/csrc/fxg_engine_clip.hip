@@ -3,12 +3,9 @@
 // single-unit build) all of them.  fxg_launch_clip (fxg_engine.hip) asks the units in turn.
 #include "fxg_host.h"
 
-// (fxg_make_plan: pl.block is FXG_CLIP_TBLOCK for the buckets of up to 16 columns and FXG_TBLOCK for every other instance; pl.ck_per_wg is 0 unless a
-// bucket of more than 16 columns runs its two-pass form)
-#define FXG_CLIP_LAUNCH(K, NAME) return fxg_launch_tiles(c, K, NAME, pl.ka, pl.lds, ctr, pl.block, false, pl.ck_per_wg);
 // a packed instance: the DP over the staged tile, or over the batch (fxg_plan.h: clip_global)
-#define FXG_CLIP_CASE_PACKED(N) case -N: FXG_CLIP_LAUNCH((pl.ka.clip_global ? fxg_kernel_tiles<-N, 0, true> : fxg_kernel_tiles<-N, 0, false>), "fxg_kernel_tiles<-" #N ",0> clip(packed)[+qtrim+qfilter]")
-#define FXG_CLIP_CASE_GENERAL(N) case N: FXG_CLIP_LAUNCH((fxg_kernel_tiles<N, 0>), "fxg_kernel_tiles<" #N ",0> clip[+qtrim+qfilter]")
+#define FXG_CLIP_CASE_PACKED(N) case -N: return fxg_launch_tiles(c, (pl.ka.clip_global ? fxg_kernel_tiles<-N, 0, true> : fxg_kernel_tiles<-N, 0, false>), pl, ctr);
+#define FXG_CLIP_CASE_GENERAL(N) case N: return fxg_launch_tiles(c, fxg_kernel_tiles<N, 0>, pl, ctr);
 #define FXG_CLIP_DEFINE_UNIT(K) \
     int FXG_CLIP_UNIT_FN(K)(fxg_ctx *c, FxgPlan &pl, u64 *ctr) { switch (pl.amax) { FXG_CLIP_UNIT(K)(FXG_CLIP_CASE_PACKED, FXG_CLIP_CASE_GENERAL) default: return FXG_CLIP_NOT_MINE; } }
 

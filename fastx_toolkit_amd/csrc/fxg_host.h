@@ -40,8 +40,7 @@ struct fxg_ctx {
     int attr_next;          // next slot to evict
     void *lds_kernel[32];   // largest MaxDynamicSharedMemorySize set per kernel (the attribute is only ever raised)
     u32 lds_max[32];
-    int env_blocks_per_cu, env_ticket_groups;   // tuning knobs, read once
-    int env_workers, env_nscan;                 // test knobs: cap on the worker workgroups of a launch / forced number of scanner waves (fxg_kernel_rows)
+    FxgKnobs knobs;         // the CONTEXT rows of fxg_knobs.h, read once (fxg_ctx_create)
     u32 *errflag;           // [0] device error bits; tile dispensers start at word FXG_TICKET_STRIDE
     u64 *counters_scratch;  // used when the caller passes no counter block
     u64 *text_ws;           // newline census / scan levels / format items
@@ -67,7 +66,6 @@ struct fxg_ctx {
     struct { fxg_batch in; fxg_params p; fxg_out out; bool hist; u32 estride; int valid; } fb_req;      // the request (fxg_run_pipeline)
     u64 *fb_blk; size_t fb_blk_cap;     // block sums / prefixes of the fallback
     int recoveries;                     // launches redone that way since the context was made (fxg_scan_recoveries)
-    int test_force_timeout;             // FXG_TEST_SCAN_TIMEOUT=1: every compacting launch starts with the time-out flag up (GPU tier)
     // barcode splitter (fxg_barcode_prepare / _split): the encoded table and the workspace of the per-(bin, tile) counts
     struct FxgBcEntry *bc_tab;
     size_t bc_tab_cap;                  // in entries
@@ -109,6 +107,16 @@ FXG_INTERNAL int fxg_enqueue_finish_counters(fxg_ctx *c, const FxgKArgs &ka, u64
 FXG_CLIP_FOR_UNITS(FXG_CLIP_DECLARE_UNIT)
 
 #define FXG_LAUNCH(c, kernel, grid, block, lds, ...) do { hipLaunchKernelGGL(kernel, dim3(grid), dim3(block), lds, (c)->stream, __VA_ARGS__); FXG_HIP(c, hipGetLastError()); } while (0)      // one launch on the context's stream, checked
+// with profiling on, what is queued between the pair is one entry of the event ring (fxg_last_kernel_ms, fxg_profiled_kernel_ms)
+#define FXG_PROFILE_BEGIN(c) do { if ((c)->profiling) FXG_HIP(c, hipEventRecord((c)->kev0[(c)->kev_count % FXG_KEV_RING], (c)->stream)); } while (0)
+#define FXG_PROFILE_END(c) do { if ((c)->profiling) { FXG_HIP(c, hipEventRecord((c)->kev1[(c)->kev_count % FXG_KEV_RING], (c)->stream)); (c)->kev_count++; } } while (0)
+
+// what fxg_last_launch_info reports: the dominant kernel of the last call and its geometry
+static inline void fxg_note_launch(fxg_ctx *c, const char *kname, u32 grid, u32 block, u32 lds, u32 tile)
+{
+    snprintf(c->last_kernel, sizeof c->last_kernel, "%s", kname);
+    c->last_grid = grid; c->last_block = block; c->last_lds = lds; c->last_tile = tile;
+}
 
 // A workspace that only grows: at least `need` units at p afterwards.  A block too small goes, after the work queued on the stream that may still use it, and
 // one of `cap` units (need plus the site's margin; `bytes` where that is not cap elements of T) takes its place: p and have are null / 0 if that allocation fails.  *fresh: the block is new.
@@ -150,23 +158,28 @@ static int fxg_kernel_fit(fxg_ctx *c, K kernel, const char *kname, u32 lds, int 
 // u64 words of the inter-workgroup state for `cap` tiles: totals, two prefixes per tile, two per scanner batch (batches of >= 256 tiles)
 #define FXG_STATUS_WORDS(cap) (3 * (size_t)(cap) + 2 * ((size_t)(cap) / 256 + 2))
 
+// one instance of a tile kernel for a planned pass (the instance tables: fxg_instances.h, fxg_clip_instances.h)
 template <typename K>
-static int fxg_launch_tiles(fxg_ctx *c, K kernel, const char *kname, FxgKArgs &ka, u32 lds, u64 *counters, u32 block = FXG_TBLOCK, bool rows_kernel = false, u64 ck_per_wg = 0)
+static int fxg_launch_tiles(fxg_ctx *c, K kernel, FxgPlan &pl, u64 *counters, bool rows_kernel = false)
 {
+    FxgKArgs &ka = pl.ka;
+    const char *const kname = fxg_inst_name(pl.inst, pl.amax);
+    const u32 lds = pl.lds, block = pl.block;
+    const u64 ck_per_wg = pl.ck_per_wg;
     FXG_HIP(c, hipSetDevice(c->device));
     int per_cu = 0;
     FXG_TRY(fxg_kernel_fit(c, kernel, kname, lds, &per_cu, block));
     // Tiles are dispensed by ticket, so nothing depends on every workgroup being resident: fill the chip.
     const int most = block == 64u ? 16 : 8;      // single-wave workgroups (fxg_rows.h, the two-pass clip instances): the LDS allows sixteen per CU
     int use = per_cu > most ? most : per_cu;
-    if (c->env_blocks_per_cu > 0) use = c->env_blocks_per_cu;
+    if (c->knobs.blocks_per_cu > 0) use = c->knobs.blocks_per_cu;
     u64 workers = (u64)c->cus * (u64)use;
-    if (c->env_workers > 0 && workers > (u64)c->env_workers) workers = (u64)c->env_workers;
+    if (c->knobs.workers > 0 && workers > (u64)c->knobs.workers) workers = (u64)c->knobs.workers;
     if (workers > ka.ntiles) workers = ka.ntiles;
     if (workers < 1) workers = 1;
     // more workgroups: the scanner(s) (fxg_device.h); fxg_kernel_rows runs several once there is work for them
     ka.nscan = !ka.compact ? 0u : (rows_kernel && workers >= 64u * FXG_ROWS_NSCAN ? (u32)FXG_ROWS_NSCAN : 1u);
-    if (ka.compact && rows_kernel && c->env_nscan > 0) ka.nscan = (u32)c->env_nscan;
+    if (ka.compact && rows_kernel && c->knobs.nscan > 0) ka.nscan = (u32)c->knobs.nscan;
     const u64 grid = workers + ka.nscan;
 
     if (ka.compact) {
@@ -197,22 +210,21 @@ static int fxg_launch_tiles(fxg_ctx *c, K kernel, const char *kname, FxgKArgs &k
     ka.tally = (u64 *)(c->errflag + 32);
     // Dispenser g serves the workgroups with blockIdx % groups == g, so every group needs a worker even if the scanner role
     // falls to its members: eight groups only when each has more workgroups than there are scanners.
-    { u32 g = c->env_ticket_groups > 0 ? (u32)c->env_ticket_groups : FXG_TICKET_GROUPS; ka.ticket_groups = grid >= (u64)(ka.nscan + 1u) * g ? g : 1u; }
+    { u32 g = c->knobs.ticket_groups > 0 ? (u32)c->knobs.ticket_groups : FXG_TICKET_GROUPS; ka.ticket_groups = grid >= (u64)(ka.nscan + 1u) * g ? g : 1u; }
     FXG_HIP(c, hipMemsetAsync(c->errflag, 0, (FXG_CTRL_WORDS + FXG_TICKET_GROUPS * FXG_TICKET_STRIDE) * sizeof(u32), c->stream));
     c->fb.valid = 0;
     if (ka.compact) {                            // what fxg_read_counters needs to do this launch again should its waits time out
         c->fb.ka = ka; c->fb.counters = counters; c->fb.valid = 1;
-        if (c->test_force_timeout) {             // "somebody already gave up": every wait of this launch that lasts ends without a result
+        if (c->knobs.test_scan_timeout) {            // "somebody already gave up": every wait of this launch that lasts ends without a result
             static const u32 up = FXG_DEV_ERR_SCAN_TIMEOUT;
             FXG_HIP(c, hipMemcpyAsync(c->errflag, &up, sizeof up, hipMemcpyHostToDevice, c->stream));
         }
     }
 
-    if (c->profiling) FXG_HIP(c, hipEventRecord(c->kev0[c->kev_count % FXG_KEV_RING], c->stream));
+    FXG_PROFILE_BEGIN(c);
     FXG_LAUNCH(c, kernel, (u32)grid, block, lds, ka);
-    if (c->profiling) { FXG_HIP(c, hipEventRecord(c->kev1[c->kev_count % FXG_KEV_RING], c->stream)); c->kev_count++; }
+    FXG_PROFILE_END(c);
     FXG_TRY(fxg_enqueue_finish_counters(c, ka, counters));      // -v report counters: the tile kernel tallied them; one tiny kernel lays them out
-    snprintf(c->last_kernel, sizeof c->last_kernel, "%s", kname);
-    c->last_grid = (u32)grid; c->last_block = block; c->last_lds = lds; c->last_tile = ka.tile_reads;
+    fxg_note_launch(c, kname, (u32)grid, block, lds, ka.tile_reads);
     return FXG_OK;
 }

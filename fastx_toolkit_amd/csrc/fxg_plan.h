@@ -1,14 +1,14 @@
 // fxg_plan.h -- host side of fxg_run_pipeline: validation of a request, folding of the tool parameters into launch arguments, the clip-history
-// decision and the clip source of a plan.  The engine (fxg_engine.hip) and the CPU emulator (tests/emu) compile this one copy; the host-only steps
-// of the other entry points sit in their family headers (fxg_history.h, fxg_stats.h, fxg_text.h, fxg_barcode.h) in the same way.
+// decision, the kernel instance (fxg_instances.h) and the clip source of a plan.  The engine (fxg_engine.hip) and the CPU emulator (tests/emu) compile
+// this one copy, and the environment reaches it only as the FxgKnobs its caller read (fxg_knobs.h); the host-only steps of the other entry points sit
+// in their family headers (fxg_history.h, fxg_stats.h, fxg_text.h, fxg_barcode.h) in the same way.
 #pragma once
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 
-#include "fxg_clip_instances.h"
-#include "fxg_kernels.h"
-#include "fxg_rows.h"
+#include "fxg_instances.h"
+#include "fxg_knobs.h"
 
 static_assert(fxg_clip_bucket(1) != 0 && fxg_clip_bucket(FXG_MAX_ADAPTER) != 0, "every adapter length the plan accepts needs a packed clip instance");
 
@@ -17,18 +17,19 @@ struct FxgPlan {
     bool group_a;   // [CLIP][QTRIM][QFILTER] chain (else [REVCOMP][FTRIM*] unless mode3/mode4)
     bool clip, use_q, rev;
     bool mask, artifacts;
+    int  inst;      // the kernel instance (FxgInst, fxg_instances.h); FXG_INST_CLIP: the clip instance of amax
+    int  rows_nw;   // of that instance's table row: != 0, it is a rows kernel (fxg_rows.h) whose lanes hold rows_nw dwords of a quality row each,
+    int  rows_h;    // with rows_h lanes per read
     int  amax;      // adapter bucket of the clip kernel instance (0 = no clip)
     u32  lds;       // dynamic LDS bytes per workgroup
-    int  rows_nw;   // != 0: the quality stages run as fxg_kernel_rows<rows_nw, rows_h> (fxg_rows.h): dwords of one lane's piece of a row
-    int  rows_h;    // lanes per read of that instance (1: rows up to 152 bytes, 2: up to 304)
-    int  rows_r;    // reads per lane (fxg_kernel_rows_multi: rows of 28..79 bytes; else 1)
-    u32  block;     // threads per workgroup of the instance (FxgTileBlock)
+    u32  block;     // threads per workgroup of the instance (fxg_instances.h: fxg_tile_block, held against FxgTileBlock there)
     u64  ck_per_wg; // floats of checkpoint scratch per workgroup (fxg_clip_two_pass_k), 0 = the instance runs its one-pass form
 };
 
 static inline int fxg_clampi(long long v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : (int)v); }
 
-static inline u32 fxg_pick_tile(u32 stride, bool clip, u32 block = FXG_TBLOCK)
+// (kn, here and below: the knobs as the caller read them; a caller that passes none plans under the environment as it is now)
+static inline u32 fxg_pick_tile(u32 stride, bool clip, u32 block = FXG_TBLOCK, const FxgKnobs &kn = fxg_knobs_read(FXG_KNOBS_REQUEST))
 {
     // Rows one workgroup covers per tile.  Streaming kernels: about 20 KB (128 reads of 150 bases) -- with the central scanner the
     // per-tile cost is small enough that the shorter pipeline step wins (cfg2: 4.13 ms at 128 reads, 4.19-4.31 at 256, 5.9 at 64;
@@ -36,8 +37,7 @@ static inline u32 fxg_pick_tile(u32 stride, bool clip, u32 block = FXG_TBLOCK)
     // more workgroups share a CU.
     const u64 budget = clip ? 60ull * 1024 : 20ull * 1024;
     u32 T = block;                          // one thread decides one read
-    const char *env = getenv("FXG_TILE");   // tuning knob: 1..block, power of two
-    if (env && atoi(env) >= 1 && atoi(env) <= (int)block && (atoi(env) & (atoi(env) - 1)) == 0) return (u32)atoi(env);
+    if (kn.tile >= 1 && kn.tile <= (int)block && (kn.tile & (kn.tile - 1)) == 0) return (u32)kn.tile;   // FXG_TILE: 1..block, power of two
     while (T > 1 && (u64)T * stride > budget) T >>= 1;
     return T;
 }
@@ -53,7 +53,8 @@ static inline FxgLds fxg_plan_layout(const FxgPlan *pl)
 static inline u32 fxg_plan_lds(const FxgPlan *pl) { return fxg_plan_layout(pl).total; }
 
 // clip_stride: row stride of the array the clipper's DP reads when it is not the batch itself (clip history), else 0
-static inline int fxg_make_plan(const fxg_batch *in, const fxg_params *p, const fxg_out *out, FxgPlan *pl, char *err, size_t cap, u32 clip_stride = 0)
+static inline int fxg_make_plan(const fxg_batch *in, const fxg_params *p, const fxg_out *out, FxgPlan *pl, char *err, size_t cap, u32 clip_stride = 0,
+                                const FxgKnobs &kn = fxg_knobs_read(FXG_KNOBS_REQUEST))
 {
     const u32 st = p->stages;
     const bool ga = (st & (FXG_STAGE_CLIP | FXG_STAGE_QTRIM | FXG_STAGE_QFILTER)) != 0;
@@ -123,10 +124,10 @@ static inline int fxg_make_plan(const fxg_batch *in, const fxg_params *p, const 
     ka.clip_ck_rows = (ka.clip_stride + 7u) / 8u < 4u ? 4u : (ka.clip_stride + 7u) / 8u;      // (rows - 1) / clip_ck_rows <= FXG_CK_SLOTS
     const u32 span_k = (u32)ka.alen + ((u32)ka.alen + 1u) / 5u;
     // (a tenth of the read as margin: with 65..73 columns on 100-base reads -- 91..99 of 100 rows -- the two passes were 7-13 % behind the one)
-    const bool two_pass_k = kform && (span_k + ka.clip_ck_rows + ka.clip_stride / 10u <= ka.clip_stride || ka.clip_stride > 255u) && !getenv("FXG_CLIP_K_ONE_PASS");
+    const bool two_pass_k = kform && (span_k + ka.clip_ck_rows + ka.clip_stride / 10u <= ka.clip_stride || ka.clip_stride > 255u) && !kn.clip_k_one_pass;
     pl->ck_per_wg = 0;
     ka.clip_ck = nullptr;
-    if (pl->clip && (ka.clip_stride <= 255u || two_pass_k || !kform) && !getenv("FXG_NO_PACKED_CLIP")) {
+    if (pl->clip && (ka.clip_stride <= 255u || two_pass_k || !kform) && !kn.no_packed_clip) {
         const int b = fxg_clip_bucket(ka.alen);      // the smallest instance that holds the adapter
         pl->amax = -b;
         if (two_pass_k) pl->ck_per_wg = (u64)FXG_CK_SLOTS * (u64)b * FXG_TBLOCK;
@@ -148,20 +149,15 @@ static inline int fxg_make_plan(const fxg_batch *in, const fxg_params *p, const 
     // wherever it exists (tests, measurements), FXG_ROWS=0 never.
     // Rows of 28..79 bytes (round 6): the same kernel with several reads per lane (fxg_kernel_rows_multi: 4 x 40, 3 x 56, 2 x 80 bytes), so that a tile is ~10 KB
     // again -- 36-base reads 0.44 -> ... of the HBM peak (profiles/r06/rows_multi_short_reads.txt).
-    pl->rows_nw = 0; pl->rows_h = 1; pl->rows_r = 1;
-    {
-        const int want = getenv("FXG_ROWS") ? atoi(getenv("FXG_ROWS")) : 1;
-        const u32 top = want >= 2 ? 304u : 208u;
-        if (ga && !pl->clip && ka.compact && in->stride >= 80u && in->stride <= top && want != 0) {
-            pl->rows_h = in->stride <= 152u ? 1 : 2;
-            pl->rows_nw = in->stride <= 104u * (u32)pl->rows_h ? 26 : 38;
-        } else if (ga && !pl->clip && ka.compact && in->stride >= 28u && in->stride < 80u && want != 0) {
-            if (in->stride <= 40u) { pl->rows_nw = 10; pl->rows_r = 4; }
-            else if (in->stride <= 56u) { pl->rows_nw = 14; pl->rows_r = 3; }
-            else { pl->rows_nw = 20; pl->rows_r = 2; }
-        }
-    }
-    pl->block = pl->rows_nw ? 64u : (ga && pl->amax < 0 && pl->amax >= -16) ? (u32)FXG_CLIP_TBLOCK : (u32)FXG_TBLOCK;     // FxgTileBlock
+    const u32 S = in->stride;
+    const bool rows = ga && !pl->clip && ka.compact && kn.rows != 0 && S >= 28u && S <= (kn.rows >= 2 ? 304u : 208u);
+    pl->inst = pl->clip ? FXG_INST_CLIP
+             : rows ? (S <= 40u ? FXG_INST_MULTI4 : S <= 56u ? FXG_INST_MULTI3 : S < 80u ? FXG_INST_MULTI2
+                       : S <= 104u ? FXG_INST_ROWS26 : S <= 152u ? FXG_INST_ROWS38 : S <= 208u ? FXG_INST_ROWS26X2 : FXG_INST_ROWS38X2)
+             : ga ? FXG_INST_TILES00 : gm ? FXG_INST_TILES03 : gf ? FXG_INST_TILES04 : pl->rev ? FXG_INST_TILES02 : FXG_INST_TILES01;      // (TILES02 / TILES05: settled below)
+    const FxgInstInfo ii = fxg_inst_info[pl->inst];
+    pl->block = pl->clip ? fxg_tile_block(pl->amax, 0) : ii.block;
+    pl->rows_nw = (int)ii.nw; pl->rows_h = (int)ii.h;
     // The two-pass clip forms can run their DP straight over the batch in global memory (fxg_clip_two_pass<.., GL>, fxg_clip_two_pass_k<.., GL>): no tile of
     // bases in LDS, so the tile stays at one read per thread whatever the read length.  Staged, a 256-thread workgroup holds 128 reads at
     // 250-300 bases and 32 at 1 000 (the other lanes idle), and from about 180 bases on a CU holds two workgroups instead of three or four.
@@ -170,12 +166,11 @@ static inline int fxg_make_plan(const fxg_batch *in, const fxg_params *p, const 
     // 300 bases 6.26 / 4.66 per 6 M, 1 000 bases 13.1 / 5.95 per 2 M: profiles/r04/ae_clip_global_vs_staged*.txt).  Rows must start on dword
     // boundaries; runs with clip history (ragged input of the tools) keep the staged form.  FXG_CLIP_GLOBAL=0 / 1 overrides (tests run both).
     ka.clip_global = 0u;
-    u32 T = pl->rows_nw ? 64u * (u32)pl->rows_r / (u32)pl->rows_h : fxg_pick_tile(pl->clip ? ka.clip_stride : in->stride, pl->clip, pl->block);
+    u32 T = pl->rows_nw ? FXG_ROWS_T * ii.r / ii.h : fxg_pick_tile(pl->clip ? ka.clip_stride : in->stride, pl->clip, pl->block, kn);
     if (pl->clip && pl->amax < 0 && (pl->amax >= -16 || pl->ck_per_wg != 0) && clip_stride == 0u && (ka.clip_stride & 3u) == 0u && ((uintptr_t)ka.clip_src & 3u) == 0u) {      // (clip_stride != 0: a run with clip history, whose rows are settled after the plan)
         ka.tile_reads = T; ka.depth = 2u;
         const bool cramped = T < pl->block || (156u * 1024u) / fxg_plan_lds(pl) < 3u;
-        const char *e = getenv("FXG_CLIP_GLOBAL");
-        ka.clip_global = (e ? atoi(e) != 0 : cramped) ? 1u : 0u;
+        ka.clip_global = (kn.clip_global >= 0 ? kn.clip_global != 0 : cramped) ? 1u : 0u;      // FXG_CLIP_GLOBAL
         if (ka.clip_global) T = pl->block;
     }
     const u64 ntiles = (in->n + T - 1) / T;
@@ -195,7 +190,8 @@ static inline int fxg_make_plan(const fxg_batch *in, const fxg_params *p, const 
         const u32 A = (in->stride + cur) & 3u, C = (in->fixed_len - start) & 3u;
         ka.rev_dw = ((A == 0u && C != 0u) || (A == 2u && (C & 1u))) ? 1u : 0u;
     }
-    if (const char *e = getenv("FXG_REV_DW")) ka.rev_dw = atoi(e) != 0 ? 1u : 0u;
+    if (kn.rev_dw >= 0) ka.rev_dw = (u32)kn.rev_dw;
+    if (pl->inst == FXG_INST_TILES02 && ka.rev_dw) pl->inst = FXG_INST_TILES05;
     // clip instances: the write-out runs two steps behind the decision (three slots) unless the extra slot costs a workgroup per CU
     ka.depth = 2u;
     if (pl->clip && FXG_CLIP_DEPTH >= 3u) {
@@ -203,8 +199,7 @@ static inline int fxg_make_plan(const fxg_batch *in, const fxg_params *p, const 
         const u32 cu_lds = 156u * 1024u, regs_wg = pl->block == 64u ? 16u : 4u;      // workgroups per CU the registers allow (128 VGPRs)
         const u32 lds2 = fxg_plan_lds(pl);
         const u32 wg2 = cu_lds / lds2 < regs_wg ? cu_lds / lds2 : regs_wg;
-        u32 want = FXG_CLIP_DEPTH;
-        { const char *e = getenv("FXG_CLIP_DEPTH_RT"); if (e && atoi(e) >= 2 && atoi(e) <= 4) want = (u32)atoi(e); }      // tuning knob
+        const u32 want = kn.clip_depth ? (u32)kn.clip_depth : FXG_CLIP_DEPTH;      // FXG_CLIP_DEPTH_RT
         for (u32 d = want; d >= 3u; --d) {           // the deepest pipeline that does not cost a workgroup per CU
             ka.depth = d;
             const u32 ldsd = fxg_plan_lds(pl);
@@ -213,7 +208,7 @@ static inline int fxg_make_plan(const fxg_batch *in, const fxg_params *p, const 
         }
         if (want == 2u) ka.depth = 2u;
     }
-    pl->lds = pl->rows_nw ? fxg_rows_lds(ka.stride, (u32)pl->rows_h, (u32)pl->rows_r) : fxg_plan_lds(pl);
+    pl->lds = pl->rows_nw ? fxg_rows_lds(ka.stride, ii.h, ii.r) : fxg_plan_lds(pl);
     return FXG_OK;
 }
 
@@ -229,9 +224,9 @@ static inline void fxg_plan_clip_from_batch(FxgPlan *pl, const fxg_batch *in) { 
 // The plan of a request on a context whose clip history is on or off (hist_wcap: the widest row so far).  *hist: this batch goes through the
 // history pre-pass (fxg_history.h), whose extended queries have rows of *estride bytes: the DP may have to run over rows as wide as anything seen so far.
 static inline int fxg_plan_request(const fxg_batch *in, const fxg_params *p, const fxg_out *out, bool hist_on, u32 hist_wcap, FxgPlan *pl, bool *hist, u32 *estride,
-                                   char *err, size_t cap)
+                                   char *err, size_t cap, const FxgKnobs &kn = fxg_knobs_read(FXG_KNOBS_REQUEST))
 {
     *hist = hist_on && (p->stages & FXG_STAGE_CLIP) && in->n != 0;
     *estride = *hist && hist_wcap > in->stride ? hist_wcap : in->stride;
-    return fxg_make_plan(in, p, out, pl, err, cap, *hist ? *estride : 0u);
+    return fxg_make_plan(in, p, out, pl, err, cap, *hist ? *estride : 0u, kn);
 }

@@ -49,18 +49,13 @@ static void emu_rows_decide_nw(const FxgKArgs &a, int h, u32 read, u32 *keep, u3
     const u32 low = fxg_rows_piece_low<NW>(a, q0, G0, fxg_rows_piece_len(cl, HB, 0)) + fxg_rows_piece_low<NW>(a, q1, G1, fxg_rows_piece_len(cl, HB, 1));
     a.res[read] = fxg_rows_verdict(a, rl, k, low, keep, olen);
 }
-static void emu_rows_decide(int nw, int h, const FxgKArgs &a, u32 read, u32 *keep, u32 *olen)
-{
-    if (nw == 10) emu_rows_decide_nw<10>(a, h, read, keep, olen);           // (fxg_kernel_rows_multi: the same decision, shorter register rows)
-    else if (nw == 14) emu_rows_decide_nw<14>(a, h, read, keep, olen);
-    else if (nw == 20) emu_rows_decide_nw<20>(a, h, read, keep, olen);
-    else if (nw == 26) emu_rows_decide_nw<26>(a, h, read, keep, olen);
-    else emu_rows_decide_nw<38>(a, h, read, keep, olen);
-}
 
-template <int AMAX, bool REV, int MODE = 0>
+// one instance: AMAX, REV, MODE as fxg_kernel_tiles has them; NW != 0: the decision of a rows kernel (fxg_kernel_rows<NW, H>; fxg_kernel_rows_multi: the same
+// decision, shorter register rows) in the tile kernel's frame
+template <int AMAX, bool REV, int MODE = 0, int NW = 0, int H = 1>
 static int emu_run(const FxgPlan &pl, uint64_t *counters, char *err, size_t cap)
 {
+    constexpr bool group_a = MODE == 0;      // the [CLIP][QTRIM][QFILTER] chain
     const FxgKArgs &a = pl.ka;
     const u32 T = a.tile_reads, stride = a.stride, NT = FXG_TBLOCK;
     std::vector<unsigned char> lds(fxg_plan_lds(&pl) + 64, 0);   // the general tile layout, also where the engine would pick fxg_kernel_rows
@@ -77,20 +72,20 @@ static int emu_run(const FxgPlan &pl, uint64_t *counters, char *err, size_t cap)
     u64 base_c = 0, base_b = 0;
     u32 bad = 0;
     std::vector<u32> keep(T), olen(T), anchor(T);
-    if (pl.group_a && fxg_clip_uses_ptab(AMAX)) { for (u32 tid = 0; tid < NT; ++tid) fxg_clip_ptab_build(a, smem + L.off_ptab, tid, NT); }
+    if (group_a && fxg_clip_uses_ptab(AMAX)) { for (u32 tid = 0; tid < NT; ++tid) fxg_clip_ptab_build(a, smem + L.off_ptab, tid, NT); }
     for (u32 tile = 0; tile < a.ntiles; ++tile) {
         const u32 r0 = tile * T;
         const u64 left = a.n - (u64)r0;
         const u32 nreads = left < (u64)T ? (u32)left : T;
         const u64 tb = (u64)r0 * stride;
         const u32 tbytes = nreads * stride;
-        if (pl.group_a) {
+        if (group_a) {
             for (u32 tid = 0; tid < NT; ++tid) {
                 if (pl.use_q) fxg_phase_bitmaps(a, tb, tbytes, bm_g, bm_l, tid, NT);
                 if constexpr (AMAX != 0) { if (!a.clip_global) fxg_phase_stage_bases(a.clip_src, a.clip_total, (u64)r0 * a.clip_stride, nreads * a.clip_stride, sb, tid, NT); }
             }
             for (u32 tid = 0; tid < nreads; ++tid) {
-                if (AMAX == 0 && pl.rows_nw) emu_rows_decide(pl.rows_nw, pl.rows_h, a, r0 + tid, &keep[tid], &olen[tid]);   // what a lane of fxg_kernel_rows does
+                if constexpr (NW != 0) emu_rows_decide_nw<NW>(a, H, r0 + tid, &keep[tid], &olen[tid]);   // what a lane of fxg_kernel_rows does
                 else if (AMAX < -16 && pl.ck_per_wg) {        // the two-pass form with its checkpoint scratch (here: one thread's, stride 1)
                     std::vector<float> ck((size_t)FXG_CK_SLOTS * (size_t)(AMAX < 0 ? fxg_clip_cols(AMAX) : 1), (getenv("FXG_EMU_CK_FILL") ? (float)atof(getenv("FXG_EMU_CK_FILL")) : 1.0e30f));   // the device's scratch is not cleared either
                     const uint8_t *pt = fxg_clip_uses_ptab(AMAX) ? smem + L.off_ptab : nullptr;
@@ -221,32 +216,68 @@ static void emu_hist_prepass(fxg_emu_hist *hs, const fxg_batch *in, u32 estride,
     fxg_hist_advance(in, &hs->cur, &hs->wcap);
 }
 
-// what fxg_make_plan chose for the last pipeline call: the clip instance (FxgPlan.amax) and whether it runs its two-pass form with checkpoints in scratch
-static int g_last_amax, g_last_two_pass, g_last_clip_global, g_last_tile;
-extern "C" void fxg_emu_last_plan(int *amax, int *two_pass) { *amax = g_last_amax; *two_pass = g_last_two_pass; }
-extern "C" void fxg_emu_last_plan_clip_global(int *on, int *tile_reads) { *on = g_last_clip_global; *tile_reads = g_last_tile; }
+// What fxg_make_plan chose for a request, as the engine would launch and report it (fxg_last_launch_info): the plan-only door of the CPU tier.  The plan never
+// dereferences the batch, so any aligned addresses and any n will do.  (tests/emu_py.py: PlanInfo)
+struct fxg_emu_plan_info {
+    char name[96];                          // of the instance (fxg_instances.h)
+    int amax, two_pass, clip_global;        // the clip instance (FxgPlan.amax), whether it runs its two-pass form with checkpoints in scratch, its DP over the batch
+    u32 tile, block, lds;
+};
+static fxg_emu_plan_info emu_plan_info(const FxgPlan &pl)
+{
+    fxg_emu_plan_info f = {};
+    const char *name = fxg_inst_name(pl.inst, pl.amax);
+    snprintf(f.name, sizeof f.name, "%s", name ? name : "");
+    f.amax = pl.amax; f.two_pass = pl.ck_per_wg != 0; f.clip_global = (int)pl.ka.clip_global;
+    f.tile = pl.ka.tile_reads; f.block = pl.block; f.lds = pl.lds;
+    return f;
+}
+extern "C" int fxg_emu_plan(const fxg_batch *in, const fxg_params *p, const fxg_out *out, int hist_on, u32 hist_wcap, fxg_emu_plan_info *info, char *err, size_t cap)
+{
+    FxgPlan pl;
+    bool hist; u32 estride;
+    const int rc = fxg_plan_request(in, p, out, hist_on != 0, hist_wcap, &pl, &hist, &estride, err, cap, fxg_knobs_read(FXG_KNOBS_REQUEST));
+    if (rc == FXG_OK) *info = emu_plan_info(pl);
+    return rc;
+}
+static fxg_emu_plan_info g_last_plan;      // of the last pipeline call
+extern "C" void fxg_emu_last_plan(int *amax, int *two_pass) { *amax = g_last_plan.amax; *two_pass = g_last_plan.two_pass; }
+extern "C" void fxg_emu_last_plan_clip_global(int *on, int *tile_reads) { *on = g_last_plan.clip_global; *tile_reads = (int)g_last_plan.tile; }
+
+// the two tables as compiled: the names of the instances in the table's order, and every knob of one scope as fxg_knobs_read parses the environment now
+extern "C" int fxg_emu_inst_count(void) { return FXG_INST_CLIP; }
+extern "C" const char *fxg_emu_inst_name(int inst, int amax) { return fxg_inst_name(inst, amax); }
+extern "C" int fxg_emu_knobs(int scope, const char **names, long long *values, int room)
+{
+    const FxgKnobs k = fxg_knobs_read((FxgKnobScope)scope);
+    int n = 0;
+#define EMU_KNOB_EXPORT(SCOPE, FIELD, NAME, KIND, LO, HI, UNSET, WHAT) if (scope == FXG_KNOBS_##SCOPE) { if (n < room) { names[n] = NAME; values[n] = (long long)k.FIELD; } ++n; }
+    FXG_KNOB_TABLE(EMU_KNOB_EXPORT)
+#undef EMU_KNOB_EXPORT
+    return n;
+}
 
 extern "C" int fxg_emu_run_pipeline_hist(const fxg_batch *in, const fxg_params *p, const fxg_out *out, char *err, size_t cap, fxg_emu_hist *hs)
 {
     FxgPlan pl;
     bool hist; u32 estride;
-    const int rc = fxg_plan_request(in, p, out, hs != nullptr, hs ? hs->wcap : 0u, &pl, &hist, &estride, err, cap);
+    const int rc = fxg_plan_request(in, p, out, hs != nullptr, hs ? hs->wcap : 0u, &pl, &hist, &estride, err, cap, fxg_knobs_read(FXG_KNOBS_REQUEST));
     if (rc != FXG_OK) return rc;
-    g_last_amax = pl.amax; g_last_two_pass = pl.ck_per_wg != 0; g_last_clip_global = (int)pl.ka.clip_global; g_last_tile = (int)pl.ka.tile_reads;
+    g_last_plan = emu_plan_info(pl);
     if (in->n == 0) return FXG_OK;
     if (hist) emu_hist_prepass(hs, in, estride, pl);
     uint64_t *ctr = out->counters;
-    if (pl.group_a) {
-        if (pl.amax == 0) return emu_run<0, false>(pl, ctr, err, cap);
-        for (int g = 0; g < FXG_CLIP_UNITS; ++g) {
-            const int r = emu_clip_units[g](pl, ctr, err, cap);
-            if (r != EMU_NOT_MINE) return r;
-        }
-        return emu_clip_rest(pl, ctr, err, cap);
+    switch (pl.inst) {                      // the instance the plan names (fxg_instances.h)
+#define EMU_INST_RUN(ID, KERNEL, NAME, ROWS, AMAX, REV, MODE, NW, H, R) case FXG_INST_##ID: return emu_run<AMAX, REV, MODE, NW, H>(pl, ctr, err, cap);
+    FXG_INSTANCES(EMU_INST_RUN)
+#undef EMU_INST_RUN
+    default: break;
     }
-    if (pl.mask) return emu_run<0, false, 3>(pl, ctr, err, cap);
-    if (pl.artifacts) return emu_run<0, false, 4>(pl, ctr, err, cap);
-    return pl.rev ? emu_run<0, true>(pl, ctr, err, cap) : emu_run<0, false>(pl, ctr, err, cap);
+    for (int g = 0; g < FXG_CLIP_UNITS; ++g) {
+        const int r = emu_clip_units[g](pl, ctr, err, cap);
+        if (r != EMU_NOT_MINE) return r;
+    }
+    return emu_clip_rest(pl, ctr, err, cap);
 }
 
 extern "C" int fxg_emu_run_pipeline(const fxg_batch *in, const fxg_params *p, const fxg_out *out, char *err, size_t cap)

@@ -24,7 +24,7 @@ class Out(C.Structure):
 _CXX = ["hipcc", "--cuda-host-only", "-O2", "-std=c++17", "-ffp-contract=off", "-fPIC", "-Wno-pass-failed", "-DFXG_HOST_EMULATION"]
 _LINK = ["hipcc", "-shared", "-fPIC"]         # (objects only: with --cuda-host-only the driver would read them as sources)
 _CSRC = os.path.join(_HERE, "..", "fastx_toolkit_amd", "csrc")
-_EMU_DEPS = [os.path.join(_EMU, "fxg_stub_ctx.h")] + [os.path.join(_CSRC, f) for f in ("fxg_device.h", "fxg_clip_instances.h", "fxg_kernels.h", "fxg_plan.h", "fxg_text.h", "fxg_rows.h", "fxg_history.h", "fxg_stats.h")]
+_EMU_DEPS = [os.path.join(_EMU, "fxg_stub_ctx.h")] + [os.path.join(_CSRC, f) for f in ("fxg_device.h", "fxg_clip_instances.h", "fxg_instances.h", "fxg_knobs.h", "fxg_kernels.h", "fxg_plan.h", "fxg_text.h", "fxg_rows.h", "fxg_history.h", "fxg_stats.h")]
 EMU_UNITS = 8               # fxg_emu.cpp: -DFXG_EMU_TU=0 (everything but the clipper's instances) and one per unit of clip instances (csrc/fxg_clip_instances.h; tests/test_clip_instances.py)
 
 
@@ -106,7 +106,10 @@ def lib():
     if _LIB is None:
         _LIB = C.CDLL(build())
         _LIB.fxg_emu_run_pipeline.argtypes = [C.POINTER(Batch), C.c_void_p, C.POINTER(Out), C.c_char_p, C.c_size_t]
+        _LIB.fxg_emu_plan.argtypes = [C.POINTER(Batch), C.c_void_p, C.POINTER(Out), C.c_int, C.c_uint32, C.POINTER(PlanInfo), C.c_char_p, C.c_size_t]
         _LIB.fxg_emu_tile_reads.restype = C.c_uint
+        _LIB.fxg_emu_inst_name.argtypes, _LIB.fxg_emu_inst_name.restype = [C.c_int, C.c_int], C.c_char_p
+        _LIB.fxg_emu_knobs.argtypes = [C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_longlong), C.c_int]
         _LIB.fxg_emu_run_pipeline_hist.argtypes = [C.POINTER(Batch), C.c_void_p, C.POINTER(Out), C.c_char_p, C.c_size_t, C.c_void_p]
         _LIB.fxg_emu_hist_new.restype = C.c_void_p
         _LIB.fxg_emu_hist_free.argtypes = [C.c_void_p]
@@ -264,6 +267,30 @@ def run_quality_stats(bases, qual, lens, fixed_len=None, hist=None, cols=None, g
     return hist
 
 
+class PlanInfo(C.Structure):
+    """fxg_emu_plan_info (fxg_emu.cpp): what fxg_make_plan chose, as the engine would launch and report it"""
+    _fields_ = [("name", C.c_char * 96), ("amax", C.c_int), ("two_pass", C.c_int), ("clip_global", C.c_int),
+                ("tile", C.c_uint32), ("block", C.c_uint32), ("lds", C.c_uint32)]
+
+    def dict(self):
+        return dict(kernel=self.name.decode(), amax=self.amax, two_pass=bool(self.two_pass), clip_global=bool(self.clip_global),
+                    tile=self.tile, block=self.block, lds=self.lds)
+
+
+def plan(stride, params, n=1, fixed_len=None, ragged=False, qual=True, compact=True, hist=None):
+    """The plan of a request without running it, under the environment as it is now: dict(kernel, amax, two_pass, clip_global, tile, block, lds).
+    The plan never dereferences the batch: every array is one fake aligned address, so n may be anything.  hist: the widest row a context with clip
+    history has seen so far (None: no history).  A refused request raises ValueError with the engine's message."""
+    A = 1 << 20
+    bt = Batch(A, A if qual else None, A if ragged else None, int(fixed_len or stride), stride, n)
+    o = Out(A, A if compact else None, A if (compact and qual) else None, A, A, A, A)
+    info, err = PlanInfo(), C.create_string_buffer(512)
+    rc = lib().fxg_emu_plan(C.byref(bt), C.addressof(params), C.byref(o), int(hist is not None), int(hist or 0), C.byref(info), err, 512)
+    if rc != 0:
+        raise ValueError("plan rc=%d: %s" % (rc, err.value.decode()))
+    return info.dict()
+
+
 def last_plan_clip_global():
     """(clip_global, tile_reads) of the plan the last emulated run was made with (fxg_plan.h: the DP over the batch instead of a staged tile)"""
     a, t = C.c_int(), C.c_int()
@@ -276,6 +303,26 @@ def last_plan():
     a, t = C.c_int(), C.c_int()
     lib().fxg_emu_last_plan(C.byref(a), C.byref(t))
     return a.value, bool(t.value)
+
+
+def instance_names():
+    """the names of csrc/fxg_instances.h in the table's order, as the emulator was compiled with it"""
+    return [lib().fxg_emu_inst_name(i, 0).decode() for i in range(lib().fxg_emu_inst_count())]
+
+
+def clip_instance_name(amax):
+    """the name of the clip instance of `amax` (negative: packed), None where the clip table has none"""
+    s = lib().fxg_emu_inst_name(lib().fxg_emu_inst_count(), amax)
+    return None if s is None else s.decode()
+
+
+def knobs(scope):
+    """{variable: value} of every knob of one scope ("request" / "context") of csrc/fxg_knobs.h, as fxg_knobs_read parses the environment now"""
+    k = ("request", "context").index(scope)
+    n = lib().fxg_emu_knobs(k, None, None, 0)
+    names, values = (C.c_char_p * n)(), (C.c_longlong * n)()
+    assert lib().fxg_emu_knobs(k, names, values, n) == n
+    return {a.decode(): int(v) for a, v in zip(names, values)}
 
 
 # ---- the device text path (fxg_text.h) through fxg_emu_fastq_index / _pack / _format / fxg_emu_fasta_weights ----
