@@ -6,6 +6,7 @@
 #include "fxg_fallback.h"
 #include "fxg_barcode.h"
 #include "fxg_reflow.h"
+#include "fxg_uncollapse.h"
 
 extern "C" int fxg_abi_version(void) { return FXG_ABI_VERSION; }
 
@@ -40,7 +41,7 @@ extern "C" void fxg_ctx_destroy(fxg_ctx *c)
     (void)hipFree(c->status); (void)hipFree(c->errflag); (void)hipFree(c->counters_scratch);
     (void)hipFree(c->text_ws); (void)hipFree(c->text_state); (void)hipFree(c->fb_blk);
     (void)hipFree(c->hist_buf[0]); (void)hipFree(c->hist_buf[1]); (void)hipFree(c->hist_w); (void)hipFree(c->hist_ws); (void)hipFree(c->stats_ws); (void)hipFree(c->clip_ck);
-    (void)hipFree(c->bc_tab); (void)hipFree(c->bc_ws); (void)hipFree(c->rf_ws);
+    (void)hipFree(c->bc_tab); (void)hipFree(c->bc_ws); (void)hipFree(c->rf_ws); (void)hipFree(c->uc_ws);
     if (c->ev0) (void)hipEventDestroy(c->ev0);
     if (c->ev1) (void)hipEventDestroy(c->ev1);
     for (int i = 0; i < FXG_KEV_RING; ++i) { if (c->kev0[i]) (void)hipEventDestroy(c->kev0[i]); if (c->kev1[i]) (void)hipEventDestroy(c->kev1[i]); }
@@ -638,6 +639,60 @@ extern "C" int fxg_fasta_reflow(fxg_ctx *c, const uint8_t *d_text, uint64_t text
     FXG_PROFILE_END(c);
     FXG_HIP(c, hipStreamSynchronize(c->stream));
     fxg_note_launch(c, "fxg_kernel_rf_copy", c->last_grid, c->last_block, c->last_lds, c->last_tile);      // (several kernels: no one geometry to report, the last one stays)
+    return FXG_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// fastx_uncollapser (fxg_uncollapse.h): counts + scan, sizes + scans + window, copy
+// ------------------------------------------------------------------------------------------------
+// with profiling on, a call leaves three entries in the event ring (two when copy_begin > 0: the scans are the block's first call's)
+extern "C" int fxg_fasta_uncollapse(fxg_ctx *c, const uint8_t *d_text, uint64_t text_len, const uint32_t *d_line, uint64_t cap_lines, uint64_t records,
+                                    const uint16_t *d_len, const fxg_uncollapse_opts *opts, uint8_t *d_out, fxg_uncollapse_info *info)
+{
+    if (!c) return FXG_E_INVALID;
+    FXG_TRY(fxg_uc_check(d_text, text_len, d_line, cap_lines, records, d_len, opts, info, c->err, sizeof c->err));
+    FXG_HIP(c, hipSetDevice(c->device));
+    const u64 n = records, M = n + 1, words = fxg_uc_ws_words(n);
+    if (opts->copy_begin == 0) {
+        c->uc_ready = 0;
+        FXG_TRY(fxg_ws_grow(c, c->uc_ws, c->uc_ws_cap, (size_t)words, (size_t)(words + words / 4 + 4096)));
+    } else if (!c->uc_ready || c->uc_records != n || c->uc_base != opts->ordinal_base)
+        return fxg_fail(c, FXG_E_INVALID, "fxg_fasta_uncollapse: copy_begin > 0 continues a block, and the context holds no scans of %llu records numbered from %llu on",
+                        (unsigned long long)n, (unsigned long long)opts->ordinal_base + 1ull);
+    const FxgUcArgs a = fxg_uc_args(d_text, d_line, cap_lines, n, d_len, opts->ordinal_base, c->uc_ws, d_out);
+    const u32 grid = (u32)((M + FXG_BLOCK - 1) / FXG_BLOCK);
+    if (opts->copy_begin == 0) {
+        FXG_PROFILE_BEGIN(c);
+        FXG_LAUNCH(c, fxg_kernel_uc_counts, grid, FXG_BLOCK, 0, a);
+        FXG_TRY(fxg_scan_u64(c, a.cnt, M, fxg_uc_levels(a)));
+        FXG_PROFILE_END(c);
+    }
+    FXG_PROFILE_BEGIN(c);
+    if (opts->copy_begin == 0) {
+        FXG_LAUNCH(c, fxg_kernel_uc_sizes, grid, FXG_BLOCK, 0, a);
+        FXG_TRY(fxg_scan_u64(c, a.size, M, fxg_uc_levels(a)));
+        FXG_TRY(fxg_scan_u64(c, a.pieces, M, fxg_uc_levels(a)));
+    }
+    FXG_LAUNCH(c, fxg_kernel_uc_window, 1, 1, 0, a, (u64)opts->copy_begin, (u64)opts->out_cap);
+    FXG_PROFILE_END(c);
+    u64 res[FXG_UC_RES_WORDS];
+    FXG_HIP(c, hipMemcpyAsync(res, a.res, sizeof res, hipMemcpyDeviceToHost, c->stream));
+    FXG_HIP(c, hipStreamSynchronize(c->stream));                // nothing may be written before the window is known to fit
+    if (opts->copy_begin == 0) { c->uc_records = n; c->uc_base = opts->ordinal_base; c->uc_ready = 1; }
+    FxgUcWindow w;
+    FXG_TRY(fxg_uc_results(res, opts, d_out != nullptr, info, &w, c->err, sizeof c->err));
+    // the copy launches cover the window, not the block: a group of 16 lanes per record and per further piece that holds copies of it
+    const u64 hgrid = info->out_bytes ? ((w.r_hi - w.r_lo + 1) * 16 + FXG_BLOCK - 1) / FXG_BLOCK : 0, tgrid = ((w.p_hi - w.p_lo) * 16 + FXG_BLOCK - 1) / FXG_BLOCK;
+    if (hgrid > 0x7FFFFFFFull || tgrid > 0x7FFFFFFFull) {
+        memset(info, 0, sizeof *info);
+        return fxg_fail(c, FXG_E_INVALID, "fxg_fasta_uncollapse: the window holds copies of too many records or pieces for one launch (2^27 groups); give it a smaller out_cap");
+    }
+    FXG_PROFILE_BEGIN(c);
+    if (hgrid) FXG_LAUNCH(c, fxg_kernel_uc_copy_heads, (u32)hgrid, FXG_BLOCK, 0, a, w);
+    if (tgrid) FXG_LAUNCH(c, fxg_kernel_uc_copy_tails, (u32)tgrid, FXG_BLOCK, 0, a, w);
+    FXG_PROFILE_END(c);
+    FXG_HIP(c, hipStreamSynchronize(c->stream));
+    if (hgrid) fxg_note_launch(c, tgrid > hgrid ? "fxg_kernel_uc_copy_tails" : "fxg_kernel_uc_copy_heads", (u32)(tgrid > hgrid ? tgrid : hgrid), FXG_BLOCK, 0, 0);      // the larger of the two copy launches
     return FXG_OK;
 }
 

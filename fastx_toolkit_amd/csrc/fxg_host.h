@@ -75,6 +75,10 @@ struct fxg_ctx {
     size_t bc_ws_cap;                   // in u64 words
     u64 *rf_ws;                         // fxg_fasta_reflow: the items' arrays, the scans' levels, the result words (fxg_reflow.h)
     size_t rf_ws_cap;                   // in u64 words
+    u64 *uc_ws;                         // fxg_fasta_uncollapse: the records' arrays, the scans' levels, the result words (fxg_uncollapse.h); kept from window to window
+    size_t uc_ws_cap;                   // in u64 words
+    u64 uc_records, uc_base;            // what the scans in uc_ws were made for (a call with copy_begin > 0 must name the same)
+    int uc_ready;
 };
 
 __attribute__((unused)) static int fxg_fail(fxg_ctx *ctx, int code, const char *fmt, ...)

@@ -26,7 +26,7 @@ EXPORTS = [
     "fxg_last_launch_info", "fxg_set_profiling", "fxg_last_kernel_ms", "fxg_profiled_kernel_ms", "fxg_set_clip_history", "fxg_run_quality_stats",
     "fxg_fastq_index", "fxg_fastq_pack", "fxg_fastq_format", "fxg_fastq_format_opts", "fxg_fasta_weights", "fxg_host_register", "fxg_host_unregister",
     "fxg_shard_range", "fxg_epilogue", "fxg_concat_pwrite", "fxg_concat_peer", "fxg_device_count", "fxg_device_numa_node", "fxg_comm_create", "fxg_comm_destroy", "fxg_epilogue_rccl",
-    "fxg_barcode_prepare", "fxg_barcode_split", "fxg_fasta_reflow",
+    "fxg_barcode_prepare", "fxg_barcode_split", "fxg_fasta_reflow", "fxg_fasta_uncollapse",
 ]
 
 
@@ -84,6 +84,17 @@ class FxgReflowOpts(C.Structure):
 
 class FxgReflowInfo(C.Structure):
     _fields_ = [("lines", C.c_uint64), ("headers", C.c_uint64), ("consumed", C.c_uint64), ("out_bytes", C.c_uint64), ("open_bases", C.c_uint64)]
+
+
+class FxgUncollapseOpts(C.Structure):
+    _fields_ = [("ordinal_base", C.c_uint64), ("copy_begin", C.c_uint64), ("out_cap", C.c_uint64)]
+
+
+class FxgUncollapseInfo(C.Structure):
+    _fields_ = [("copies", C.c_uint64), ("copy_end", C.c_uint64), ("out_bytes", C.c_uint64)]
+
+
+UNCOLLAPSE_TEXT_MAX = 1 << 28    # FXG_UC_TEXT_MAX
 
 
 def reflow_bound(text_len):
@@ -181,6 +192,8 @@ def load_library(path=None):
     L.fxg_barcode_split.argtypes = [vp, vp, u64, i32, vp, u64, u64, vp, vp, C.POINTER(u64), C.POINTER(u64)]
     if hasattr(L, "fxg_fasta_reflow"):       # (the CPU tier's look-alike libraries predate the entry; the product library always has it, tests/test_abi.py)
         L.fxg_fasta_reflow.argtypes = [vp, vp, u64, i32, u64, C.POINTER(FxgReflowOpts), vp, u64, vp, C.POINTER(FxgReflowInfo)]
+    if hasattr(L, "fxg_fasta_uncollapse"):   # (as above)
+        L.fxg_fasta_uncollapse.argtypes = [vp, vp, u64, vp, u64, u64, vp, C.POINTER(FxgUncollapseOpts), vp, C.POINTER(FxgUncollapseInfo)]
     L.fxg_set_profiling.argtypes = [vp, i32]
     L.fxg_set_clip_history.argtypes = [vp, i32]
     L.fxg_run_quality_stats.argtypes = [vp, C.POINTER(FxgBatch), vp, C.c_uint32]
@@ -558,6 +571,21 @@ class Engine:
         self._check(self.lib.fxg_fasta_reflow(self.ctx, d_text.data_ptr(), text_len, int(bool(at_eof)), open_bases_in, C.byref(o), line.data_ptr(), cap_lines,
                                               out.data_ptr(), C.byref(info)))
         return out[:info.out_bytes], info
+
+    def fasta_uncollapse(self, d_text, text_len, ix, n, lens, out, ordinal_base=0, copy_begin=0, out_cap=None):
+        """fastx_uncollapser on one window of an indexed block of collapsed FASTA (fastq_index(fasta=True); fxg_fasta_uncollapse in
+        include/fxg.h): the longest run of whole copies from copy_begin on that fits out (or out_cap bytes of it).  Returns (view, info):
+        the view holds exactly the bytes written, info.copy_end is the next call's copy_begin until it equals info.copies.  out may be
+        None for a call that can write nothing (out_cap 0)."""
+        if not hasattr(self.lib, "fxg_fasta_uncollapse"):
+            raise FxgError("this libfxg.so has no fxg_fasta_uncollapse")
+        cap = (out.numel() if out is not None else 0) if out_cap is None else out_cap
+        o = FxgUncollapseOpts(ordinal_base, copy_begin, cap)
+        info = FxgUncollapseInfo()
+        self._after_torch()
+        self._check(self.lib.fxg_fasta_uncollapse(self.ctx, d_text.data_ptr(), text_len, ix.line.data_ptr(), ix.cap_lines, n, lens.data_ptr(), C.byref(o),
+                                                  out.data_ptr() if out is not None else None, C.byref(info)))
+        return (out[:info.out_bytes] if out is not None else None), info
 
     def read_counters(self, d_counters):
         host = (C.c_uint64 * NCOUNTERS)()

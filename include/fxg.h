@@ -187,6 +187,9 @@ typedef struct fxg_out {
  *   fasta reflow (below)     d_text: read as for the text path (text_len + 16 bytes); d_line: 2 * cap_lines uint32 as for the text path, of which
  *                            the line starts ls[0 .. lines] are read back; d_out: write exactly info->out_bytes bytes, never a byte past them,
  *                            and none at all when the request is refused.
+ *   fasta uncollapse (below) d_text: the bytes of the records' lines (text_len + 16 readable, as for the text path); d_line: 2 * cap_lines uint32,
+ *                            read at entries 0 .. 2 * records - 1 of either half; d_len: read records uint16; d_out: write exactly
+ *                            info->out_bytes bytes, never a byte past them, and none at all when the request is refused.
  * tests/test_emu_bounds.py runs the kernels' bodies with every array against a guard page at these ends; tests/test_gpu_bounds.py surrounds every
  * array with poison (inputs) and canaries (outputs) on the device. */
 
@@ -373,6 +376,36 @@ typedef struct fxg_reflow_info {
 } fxg_reflow_info;
 int  fxg_fasta_reflow(fxg_ctx *ctx, const uint8_t *d_text, uint64_t text_len, int at_eof, uint64_t open_bases_in, const fxg_reflow_opts *opts,
                       uint32_t *d_line, uint64_t cap_lines, uint8_t *d_out, fxg_reflow_info *info);
+/* fastx_uncollapser (reference src/fastx_uncollapser/fastx_uncollapser.cpp:73-98, src/libfastx/fastx.c:440-495): collapsed FASTA expanded on
+ * the device.  The block has been through fxg_fastq_index with lines_per_record == 2 (d_text, d_line, cap_lines, records and d_len as that call
+ * left them).  Record r stands for count(r) reads: the number after the first '-' of its id as atoi reads it, 1 if there is no dash or the number
+ * is not positive (fastx.c:475-495).  It goes out count(r) times as ">%llu\nBASES\n"; the numbers run through the block's copies in input
+ * order, copy g (0-based) is named ordinal_base + g + 1.  Input ids and CR bytes do not survive.
+ * The output can be many times the input, so a call writes the longest run of WHOLE copies from copy_begin on that fits out_cap bytes:
+ * copies [copy_begin, info->copy_end), info->out_bytes bytes from d_out[0] on, and the caller walks the block window by window until copy_end
+ * == info->copies.  A call with copy_begin == 0 makes the block's scans, in a workspace of the context that no other entry uses; a call with
+ * copy_begin > 0 reuses the scans of the last fxg_fasta_uncollapse call with copy_begin == 0 on this context.  That this call was on the same
+ * block is the caller's promise: the entry only notices a different number of records or another ordinal_base.  copy_begin == copies is a
+ * valid call that writes nothing.
+ * Refused (FXG_E_INVALID with a message) with d_out untouched: an out_cap smaller than copy copy_begin (the message says how many bytes it
+ * needs); copy_begin > copies; ordinal_base + copies past 2^64 - 1; a window with copies of more than 2^27 records or of more than 2^27
+ * further pieces of 16 copies (one launch each: give it a smaller out_cap; info is zeroed); text_len > 2^28.  The last one is what keeps every offset exact: byte
+ * offsets, copies and pieces are 64-bit and no scan checks for overflow.  A record takes at least four bytes of text, so 2^28 bytes hold at
+ * most 2^26 records whose (bases + 23) sum to less than 2^31, and a count is below 2^31: the block's output stays below 2^62 bytes.
+ * d_out: exactly info->out_bytes bytes are written, never a byte past them.  Synchronises.  With profiling on, a call with copy_begin == 0
+ * records three intervals: counts + scan, sizes + scans + window, copy; a later window of the block records the last two (its first: the window alone). */
+typedef struct fxg_uncollapse_opts {
+    uint64_t ordinal_base;   /* copies written by the blocks before this one: copy g of the block is named ordinal_base + g + 1 */
+    uint64_t copy_begin;     /* first copy of the block this call writes */
+    uint64_t out_cap;        /* bytes d_out can take */
+} fxg_uncollapse_opts;
+typedef struct fxg_uncollapse_info {
+    uint64_t copies;         /* of the whole block */
+    uint64_t copy_end;       /* this call wrote copies [copy_begin, copy_end) */
+    uint64_t out_bytes;      /* written to d_out */
+} fxg_uncollapse_info;
+int  fxg_fasta_uncollapse(fxg_ctx *ctx, const uint8_t *d_text, uint64_t text_len, const uint32_t *d_line, uint64_t cap_lines, uint64_t records,
+                          const uint16_t *d_len, const fxg_uncollapse_opts *opts, uint8_t *d_out, fxg_uncollapse_info *info);
 int  fxg_host_register(fxg_ctx *ctx, void *ptr, size_t bytes);     /* page-lock an existing host buffer for async copies */
 int  fxg_host_unregister(fxg_ctx *ctx, void *ptr);
 
