@@ -151,7 +151,7 @@ extern "C" int fxg_set_clip_history(fxg_ctx *c, int on)
         FXG_HIP(c, hipMemsetAsync(c->hist_buf[1], 0, FXG_HIST_CAP, c->stream));
         FXG_HIP(c, hipMemsetAsync(c->hist_w, 0, 2 * sizeof(u32), c->stream));
     }
-    c->hist_on = on ? 1 : 0; c->hist_wcap = 0; c->hist_cur = 0;
+    c->hist_on = on ? 1 : 0; c->hist_wcap = 0; c->hist_cur = 0; c->hist_has_adapter = 0;
     return FXG_OK;
 }
 
@@ -191,6 +191,12 @@ extern "C" int fxg_run_pipeline(fxg_ctx *c, const fxg_batch *in, const fxg_param
         return FXG_OK;
     }
     if (hist) {
+        // the reference's matrix keeps the height of its adapter as it keeps the width of its longest read; only the reads' side of that is reproduced, so a
+        // history has one adapter (include/fxg.h).  Refused before anything is launched: the history stays as it was.
+        if (c->hist_has_adapter && strcmp(c->hist_adapter, pl.ka.adapter) != 0)
+            return fxg_fail(c, FXG_E_INVALID, "clip history: the adapter differs from the one this history began with; fxg_set_clip_history(ctx, 1) begins another");
+        snprintf(c->hist_adapter, sizeof c->hist_adapter, "%s", pl.ka.adapter);
+        c->hist_has_adapter = 1;
         FXG_HIP(c, hipSetDevice(c->device));
         FXG_TRY(fxg_hist_prepass(c, in, estride, pl));
     }
@@ -237,8 +243,8 @@ extern "C" int fxg_run_quality_stats(fxg_ctx *c, const fxg_batch *in, uint64_t *
     a.partial = c->stats_ws;
     a.round_robin = kn.qs_round_robin;      // FXG_QS_ROUND_ROBIN (measurement knob)
     const u32 lds = FXG_QS_LDS_WORDS * sizeof(u32);
-    FXG_HIP(c, hipFuncSetAttribute((const void *)fxg_kernel_quality_stats, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    FXG_HIP(c, hipFuncSetAttribute((const void *)fxg_kernel_quality_stats_odd, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    FXG_TRY(fxg_kernel_lds(c, fxg_kernel_quality_stats, lds));
+    FXG_TRY(fxg_kernel_lds(c, fxg_kernel_quality_stats_odd, lds));
     const u32 nstrips = (in->stride + FXG_QS_STRIP - 1) / FXG_QS_STRIP;
     for (u32 s0 = 0; s0 < nstrips; s0 += FXG_QS_WAVES) {       // one pass per block of 160 columns (one pass for reads up to 160)
         a.strip0 = s0;
@@ -363,7 +369,7 @@ extern "C" int fxg_synth_generate(fxg_ctx *c, uint64_t seed, uint64_t first, uin
     const u32 lds = 2 * fxg_r16(FXG_SYNTH_TILE * stride);
     if (lds > 160 * 1024) return fxg_fail(c, FXG_E_INVALID, "synth: stride %u too large", stride);
     FXG_HIP(c, hipSetDevice(c->device));
-    FXG_HIP(c, hipFuncSetAttribute((const void *)fxg_kernel_synth, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    FXG_TRY(fxg_kernel_lds(c, fxg_kernel_synth, lds));      // (its LDS follows the stride: raised only, like the tile kernels')
     const u64 blocks = (n + FXG_SYNTH_TILE - 1) / FXG_SYNTH_TILE;
     if (blocks > 0x7FFFFFFFull) return fxg_fail(c, FXG_E_INVALID, "synth: too many reads for one launch");
     FXG_LAUNCH(c, fxg_kernel_synth, (u32)blocks, FXG_BLOCK, lds, (u64)seed, (u64)first, (u64)n, L, with_adapter, bases, qual, stride);
@@ -373,9 +379,16 @@ extern "C" int fxg_synth_generate(fxg_ctx *c, uint64_t seed, uint64_t first, uin
 // ------------------------------------------------------------------------------------------------
 // FASTQ text on the device
 // ------------------------------------------------------------------------------------------------
-static int fxg_text_reserve(fxg_ctx *c, size_t words)
+// the device-side state of the text calls: made by the first of them that needs it, whichever that is
+static int fxg_text_state_ensure(fxg_ctx *c)
 {
     if (!c->text_state) FXG_HIP(c, hipMalloc((void **)&c->text_state, sizeof(FxgTextState)));
+    return FXG_OK;
+}
+
+static int fxg_text_reserve(fxg_ctx *c, size_t words)
+{
+    FXG_TRY(fxg_text_state_ensure(c));
     const size_t cap = words + words / 4 + 4096;
     return fxg_ws_grow(c, c->text_ws, c->text_ws_cap, words, cap);
 }
@@ -454,6 +467,7 @@ extern "C" int fxg_fastq_pack(fxg_ctx *c, const uint8_t *d_text, uint64_t text_l
     const u64 nchunks = (n * (u64)stride + 15) >> 4;
     u64 grid = (nchunks + FXG_BLOCK - 1) / FXG_BLOCK;
     if (grid > 65536) grid = 65536;
+    FXG_TRY(fxg_text_state_ensure(c));      // (a context that has indexed nothing: the line arrays are another context's)
     FXG_HIP(c, hipMemsetAsync(&c->text_state->irregular, 0, sizeof(u32), c->stream));
     if (lines_per_record == 4) FXG_LAUNCH(c, (fxg_kernel_text_pack<false, 4>), (u32)grid, FXG_BLOCK, 0, d_text, (u64)text_len, d_ls, d_le, d_flags, (u64)n, stride, qoffset, d_bases, c->text_state);
     else FXG_LAUNCH(c, (fxg_kernel_text_pack<false, 2>), (u32)grid, FXG_BLOCK, 0, d_text, (u64)text_len, d_ls, d_le, d_flags, (u64)n, stride, qoffset, d_bases, c->text_state);

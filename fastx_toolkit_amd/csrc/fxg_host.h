@@ -15,6 +15,7 @@
 #include <cstring>
 #include <unistd.h>
 
+#include "fxg_attr.h"
 #include "fxg_plan.h"
 #include "fxg_rows.h"
 
@@ -34,12 +35,7 @@ struct fxg_ctx {
     u64 *status;            // FXG_STATUS_WORDS(status_cap) granules: tile totals [cap], prefixes [2 * cap], batch bases
     size_t status_cap;      // in tiles
     u32 epoch;              // tag of the granules of the current launch (1..255); 0 = never valid
-    void *attr_kernel[8];   // kernels whose launch attributes were set, with the LDS size and the occupancy answer
-    u32 attr_lds[8];
-    int attr_per_cu[8];
-    int attr_next;          // next slot to evict
-    void *lds_kernel[32];   // largest MaxDynamicSharedMemorySize set per kernel (the attribute is only ever raised)
-    u32 lds_max[32];
+    FxgFitCache fit;        // occupancy answer per (kernel, LDS size); what the kernels' LDS attributes were set to is the process's to know (fxg_attr.h)
     FxgKnobs knobs;         // the CONTEXT rows of fxg_knobs.h, read once (fxg_ctx_create)
     u32 *errflag;           // [0] device error bits; tile dispensers start at word FXG_TICKET_STRIDE
     u64 *counters_scratch;  // used when the caller passes no counter block
@@ -48,6 +44,8 @@ struct fxg_ctx {
     FxgTextState *text_state;
     // clip history (fxg_set_clip_history): the reference aligner's query buffer, carried from batch to batch
     int hist_on;
+    int hist_has_adapter;   // a batch went through this history: the adapter of every later one must be the same (one history is one reference process)
+    char hist_adapter[FXG_MAX_ADAPTER + 1];
     u32 hist_wcap;          // host-side upper bound of the buffer width (the exact width lives on the device)
     int hist_cur;           // which of hist_buf[2] / hist_w[2] is current
     uint8_t *hist_buf[2];
@@ -136,26 +134,29 @@ static int fxg_ws_grow(fxg_ctx *c, T *&p, size_t &have, size_t need, size_t cap,
     return FXG_OK;
 }
 
-// dynamic-LDS attribute and occupancy of a kernel: asked once per (kernel, LDS size), not per launch
+// The dynamic-LDS attribute of a kernel covers `lds` afterwards: set through the process's table (fxg_attr.h), which only ever raises it.  The context's device is current.
+template <typename K>
+static int fxg_kernel_lds(fxg_ctx *c, K kernel, u32 lds)
+{
+    hipError_t e = hipSuccess;
+    if (fxg_attr_cover(fxg_attr_process_table(), c->device, (const void *)kernel, lds,
+                       [&](u32 v) { e = hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)v); return e == hipSuccess ? 0 : 1; }))
+        return fxg_fail(c, FXG_E_HIP, "hipFuncSetAttribute(MaxDynamicSharedMemorySize, %u) failed: %s", lds, hipGetErrorString(e));
+    return FXG_OK;
+}
+
+// dynamic-LDS attribute and occupancy of a kernel: asked once per (kernel, LDS size), not per launch.  What is set when is fxg_fit_decide's to say (fxg_attr.h,
+// shared with the CPU tier): one kernel alternating between LDS sizes, in this context or in another one of the process, is never launched with more than was last set.
 template <typename K>
 static int fxg_kernel_fit(fxg_ctx *c, K kernel, const char *kname, u32 lds, int *per_cu, u32 block = FXG_TBLOCK)
 {
-    for (int i = 0; i < 8; ++i)
-        if (c->attr_kernel[i] == (void *)kernel && c->attr_lds[i] == lds) { *per_cu = c->attr_per_cu[i]; return FXG_OK; }
-    // the attribute is a property of the kernel, not of the cache entry: one kernel alternating between LDS sizes must never be
-    // launched with more than was last set, so it is only ever raised
-    int k = -1;
-    for (int i = 0; i < 32; ++i) { if (c->lds_kernel[i] == (void *)kernel) { k = i; break; } if (!c->lds_kernel[i] && k < 0) k = i; }
-    if (k < 0 || c->lds_kernel[k] != (void *)kernel || c->lds_max[k] < lds) {
-        FXG_HIP(c, hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        if (k >= 0) { c->lds_kernel[k] = (void *)kernel; c->lds_max[k] = lds; }
-    }
-    FXG_HIP(c, hipOccupancyMaxActiveBlocksPerMultiprocessor(per_cu, kernel, (int)block, lds));
+    hipError_t e = hipSuccess;
+    const char *what = "hipFuncSetAttribute";
+    const int rc = fxg_fit_decide(fxg_attr_process_table(), c->fit, c->device, (const void *)kernel, lds, per_cu,
+        [&](u32 v) { e = hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)v); return e == hipSuccess ? 0 : 1; },
+        [&](int *n) { what = "hipOccupancyMaxActiveBlocksPerMultiprocessor"; e = hipOccupancyMaxActiveBlocksPerMultiprocessor(n, kernel, (int)block, lds); return e == hipSuccess ? 0 : 1; });
+    if (rc != 0) return fxg_fail(c, FXG_E_HIP, "%s failed for %s (lds=%u): %s", what, kname, lds, hipGetErrorString(e));
     if (*per_cu < 1) return fxg_fail(c, FXG_E_INVALID, "%s does not fit on a CU (lds=%u)", kname, lds);
-    int slot = -1;
-    for (int i = 0; i < 8; ++i) if (!c->attr_kernel[i]) { slot = i; break; }
-    if (slot < 0) { slot = c->attr_next; c->attr_next = (c->attr_next + 1) % 8; }
-    c->attr_kernel[slot] = (void *)kernel; c->attr_lds[slot] = lds; c->attr_per_cu[slot] = *per_cu;
     return FXG_OK;
 }
 

@@ -276,7 +276,9 @@ typedef struct fxg_text_info {
  * d_flags: device u8[cap_lines / lines_per_record]. */
 int  fxg_fastq_index(fxg_ctx *ctx, const uint8_t *d_text, uint64_t text_len, int at_eof, int lines_per_record, uint32_t *d_line,
                      uint64_t cap_lines, uint16_t *d_len, uint8_t *d_flags, fxg_text_info *info);
-/* rows: device arrays of at least records * stride rounded up to 16 bytes; qualities become Phred+33 codes (d_qual NULL for FASTA). */
+/* rows: device arrays of at least records * stride rounded up to 16 bytes; qualities become Phred+33 codes (d_qual NULL for FASTA).
+ * The line arrays and flags are the caller's: they may come from fxg_fastq_index on another context of the same device, and the pack may be the
+ * first call a context ever sees (it makes what device state it needs itself). */
 int  fxg_fastq_pack(fxg_ctx *ctx, const uint8_t *d_text, uint64_t text_len, int lines_per_record, const uint32_t *d_line, uint64_t cap_lines,
                     const uint8_t *d_flags, uint64_t records, uint32_t stride, int qoffset, uint8_t *d_bases, uint8_t *d_qual, uint32_t *irregular);
 /* Writes "@name\nSEQ\n+name2\nQUAL\n" (or ">name\nSEQ\n": FASTA input, or out_fasta) for every kept record (res keep bit) in input
@@ -315,7 +317,9 @@ int  fxg_fastq_format_opts(fxg_ctx *ctx, const uint8_t *d_text, int lines_per_re
                            const uint64_t *d_pk_off, const uint8_t *d_rows_qual, uint32_t stride, int qoffset, int out_fasta, uint8_t *d_out,
                            uint64_t *out_bytes, const fxg_format_opts *opts);
 /* FASTA records stand for `count` reads when their identifier is "id-count" (fastx.c:475-495).  weighted[0..6] = read-count
- * weighted tallies over the block: input, kept, clip too-short, adapter-only, no-adapter, adapter-found, has-N. */
+ * weighted tallies over the block: input, kept, clip too-short, adapter-only, no-adapter, adapter-found, has-N.
+ * Precondition: the context has run fxg_fastq_index, fxg_fastq_pack, fxg_fastq_format[_opts] or fxg_fasta_reflow before.  On a context that has not,
+ * a call with records > 0 is refused: FXG_E_INVALID, "fxg_fasta_weights: index the block first", weighted[] all zero, nothing launched. */
 int  fxg_fasta_weights(fxg_ctx *ctx, const uint8_t *d_text, const uint32_t *d_line, uint64_t cap_lines, uint64_t records, const uint32_t *d_res,
                        uint64_t weighted[8]);
 /* fastx_barcode_splitter (reference scripts/fastx_barcode_splitter.pl): a stable partition of a block's records into `bins` bins by their
@@ -396,7 +400,11 @@ int  fxg_fasta_reflow(fxg_ctx *ctx, const uint8_t *d_text, uint64_t text_len, in
  * records three intervals: counts + scan, sizes + scans + window, copy; a later window of the block records the last two (its first: the window alone). */
 typedef struct fxg_uncollapse_opts {
     uint64_t ordinal_base;   /* copies written by the blocks before this one: copy g of the block is named ordinal_base + g + 1 */
-    uint64_t copy_begin;     /* first copy of the block this call writes */
+    uint64_t copy_begin;     /* first copy of the block this call writes.  > 0: the scans of the context's last call with copy_begin == 0 are used as they
+                              * are, and that they are THIS block's is the caller's duty: the context remembers (records, ordinal_base) and nothing of the
+                              * text (a caller reuses one buffer for block after block, so its address says nothing).  Another block with the same two
+                              * numbers is accepted and written from the other block's scans; a context with no scans, other records or another
+                              * ordinal_base is refused, "... copy_begin > 0 continues a block ...", d_out untouched. */
     uint64_t out_cap;        /* bytes d_out can take */
 } fxg_uncollapse_opts;
 typedef struct fxg_uncollapse_info {
@@ -425,7 +433,12 @@ int  fxg_run_quality_stats(fxg_ctx *ctx, const fxg_batch *in, uint64_t *d_hist, 
  * it.  With history on (on != 0; the call also resets the buffer to that of a fresh process) the CLIP stage
  * reproduces this: the reads of a batch, and of successive fxg_run_* calls on this context, form one sequence in call order.
  * Off (the default), every read is aligned on its own, which is identical for input of one fixed length.  Sharding a
- * variable-length clipper job over several contexts is only exact with history off on both sides. */
+ * variable-length clipper job over several contexts is only exact with history off on both sides.
+ * One history is one reference process, and that has ONE adapter: its matrix keeps the height of the adapter as it keeps the width of the
+ * longest read, and only the reads' side of that is reproduced here.  A CLIP run whose adapter differs from that of the first CLIP run since
+ * fxg_set_clip_history(ctx, on != 0) is refused -- FXG_E_INVALID, "clip history: the adapter differs from the one this history began with;
+ * fxg_set_clip_history(ctx, 1) begins another" -- with nothing launched, no output touched and the history as it was.  Runs without a CLIP stage,
+ * fxg_run_quality_stats and the text calls neither see nor move the history. */
 int  fxg_set_clip_history(fxg_ctx *ctx, int on);
 
 /* ---- several GPUs.  The reference is one process over one stream of reads (e.g.

@@ -291,6 +291,37 @@ def plan(stride, params, n=1, fixed_len=None, ragged=False, qual=True, compact=T
     return info.dict()
 
 
+class AttrSet(C.Structure):
+    _fields_ = [("step", C.c_uint64), ("device", C.c_int32), ("kernel", C.c_int32), ("lds", C.c_uint32)]
+
+
+_ATTR = None
+
+
+def attr_replay(launches, nctx=None):
+    """Replays launches [(context, device, kernel, lds), ...] through the engine's own decision about the kernels' dynamic-LDS attribute (csrc/fxg_attr.h,
+    compiled into tests/emu/libfxgattr.so from attr_emu.cpp): one process, one occupancy cache per context.  Returns (the log of attribute sets
+    [(step, device, kernel, lds), ...] in order, the number of occupancy questions asked)."""
+    global _ATTR
+    if _ATTR is None:
+        so, src = os.path.join(_EMU, "libfxgattr.so"), os.path.join(_EMU, "attr_emu.cpp")
+        if not os.path.exists(so) or os.path.getmtime(so) < max(os.path.getmtime(x) for x in (src, os.path.join(_CSRC, "fxg_attr.h"))):
+            subprocess.check_call(["hipcc", "--cuda-host-only", "-O2", "-std=c++17", "-fPIC", "-shared", "-Wall", "-Wextra", "-x", "c++", src, "-o", so + ".tmp", "-lpthread"])
+            os.replace(so + ".tmp", so)
+        _ATTR = C.CDLL(so)
+        _ATTR.fxg_emu_attr_replay.restype = C.c_longlong
+        _ATTR.fxg_emu_attr_replay.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_int32, C.POINTER(AttrSet), C.c_uint64, C.POINTER(C.c_uint64)]
+    a = np.array(launches, dtype=np.int64).reshape(-1, 4)
+    cols = [np.ascontiguousarray(a[:, 0], dtype=np.int32), np.ascontiguousarray(a[:, 1], dtype=np.int32), np.ascontiguousarray(a[:, 2], dtype=np.int32),
+            np.ascontiguousarray(a[:, 3], dtype=np.uint32)]
+    nctx = nctx or (int(a[:, 0].max()) + 1 if len(a) else 1)
+    log, asked = (AttrSet * max(len(a), 1))(), C.c_uint64()
+    n = _ATTR.fxg_emu_attr_replay(*[c.ctypes.data for c in cols], len(a), nctx, log, len(a), C.byref(asked))
+    if n < 0:
+        raise ValueError("attr_replay: bad sequence")
+    return [(int(log[i].step), int(log[i].device), int(log[i].kernel), int(log[i].lds)) for i in range(n)], int(asked.value)
+
+
 def last_plan_clip_global():
     """(clip_global, tile_reads) of the plan the last emulated run was made with (fxg_plan.h: the DP over the batch instead of a staged tile)"""
     a, t = C.c_int(), C.c_int()
