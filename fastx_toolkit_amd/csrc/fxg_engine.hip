@@ -7,6 +7,7 @@
 #include "fxg_barcode.h"
 #include "fxg_reflow.h"
 #include "fxg_uncollapse.h"
+#include "fxg_nucchange.h"
 
 extern "C" int fxg_abi_version(void) { return FXG_ABI_VERSION; }
 
@@ -41,7 +42,7 @@ extern "C" void fxg_ctx_destroy(fxg_ctx *c)
     (void)hipFree(c->status); (void)hipFree(c->errflag); (void)hipFree(c->counters_scratch);
     (void)hipFree(c->text_ws); (void)hipFree(c->text_state); (void)hipFree(c->fb_blk);
     (void)hipFree(c->hist_buf[0]); (void)hipFree(c->hist_buf[1]); (void)hipFree(c->hist_w); (void)hipFree(c->hist_ws); (void)hipFree(c->stats_ws); (void)hipFree(c->clip_ck);
-    (void)hipFree(c->bc_tab); (void)hipFree(c->bc_ws); (void)hipFree(c->rf_ws); (void)hipFree(c->uc_ws);
+    (void)hipFree(c->bc_tab); (void)hipFree(c->bc_ws); (void)hipFree(c->rf_ws); (void)hipFree(c->uc_ws); (void)hipFree(c->nc_res);
     if (c->ev0) (void)hipEventDestroy(c->ev0);
     if (c->ev1) (void)hipEventDestroy(c->ev1);
     for (int i = 0; i < FXG_KEV_RING; ++i) { if (c->kev0[i]) (void)hipEventDestroy(c->kev0[i]); if (c->kev1[i]) (void)hipEventDestroy(c->kev1[i]); }
@@ -707,6 +708,34 @@ extern "C" int fxg_fasta_uncollapse(fxg_ctx *c, const uint8_t *d_text, uint64_t 
     FXG_PROFILE_END(c);
     FXG_HIP(c, hipStreamSynchronize(c->stream));
     if (hgrid) fxg_note_launch(c, tgrid > hgrid ? "fxg_kernel_uc_copy_tails" : "fxg_kernel_uc_copy_heads", (u32)(tgrid > hgrid ? tgrid : hgrid), FXG_BLOCK, 0, 0);      // the larger of the two copy launches
+    return FXG_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// fasta_nucleotide_changer (fxg_nucchange.h): one launch, groups of 16 lanes that take a record at a time
+// ------------------------------------------------------------------------------------------------
+// (C linkage from its declaration in include/fxg.h.  The table of first calls in tests/context_state_cases.py lists the definitions above; this
+// entry's first call on a new context is in tests/test_gpu_nucchange.py.)
+int fxg_bases_change(fxg_ctx *c, uint8_t *d_text, uint64_t text_len, int lines_per_record, const uint32_t *d_line, uint64_t cap_lines, uint64_t records,
+                     int from, int to, fxg_bases_change_info *info)
+{
+    if (!c) return FXG_E_INVALID;
+    FXG_TRY(fxg_nc_check(d_text, text_len, lines_per_record, d_line, cap_lines, records, from, to, info, c->err, sizeof c->err));
+    if (records == 0) return FXG_OK;
+    FXG_HIP(c, hipSetDevice(c->device));
+    if (!c->nc_res) FXG_HIP(c, hipMalloc((void **)&c->nc_res, FXG_NC_RES_WORDS * sizeof(u64)));
+    u64 res[FXG_NC_RES_WORDS];
+    fxg_nc_res_init(res);
+    FXG_HIP(c, hipMemcpyAsync(c->nc_res, res, sizeof res, hipMemcpyHostToDevice, c->stream));      // (pageable: the copy is staged before the call returns)
+    const FxgNcArgs a = fxg_nc_args(d_text, lines_per_record, d_line, cap_lines, records, from, to, c->nc_res);
+    const u64 grid = fxg_nc_grid(records);                       // FXG_NC_GRID_MAX at the most
+    FXG_PROFILE_BEGIN(c);
+    FXG_LAUNCH(c, fxg_kernel_bases_change, (u32)grid, FXG_BLOCK, 0, a);
+    FXG_PROFILE_END(c);
+    FXG_HIP(c, hipMemcpyAsync(res, c->nc_res, sizeof res, hipMemcpyDeviceToHost, c->stream));
+    FXG_HIP(c, hipStreamSynchronize(c->stream));
+    fxg_nc_results(res, info);
+    fxg_note_launch(c, "fxg_kernel_bases_change", (u32)grid, FXG_BLOCK, 0, 0);
     return FXG_OK;
 }
 

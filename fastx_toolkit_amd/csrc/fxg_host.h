@@ -77,6 +77,7 @@ struct fxg_ctx {
     size_t uc_ws_cap;                   // in u64 words
     u64 uc_records, uc_base;            // what the scans in uc_ws were made for (a call with copy_begin > 0 must name the same)
     int uc_ready;
+    u64 *nc_res;                        // fxg_bases_change: the launch's result words (fxg_nucchange.h)
 };
 
 __attribute__((unused)) static int fxg_fail(fxg_ctx *ctx, int code, const char *fmt, ...)

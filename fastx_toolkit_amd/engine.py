@@ -26,7 +26,7 @@ EXPORTS = [
     "fxg_last_launch_info", "fxg_set_profiling", "fxg_last_kernel_ms", "fxg_profiled_kernel_ms", "fxg_set_clip_history", "fxg_run_quality_stats",
     "fxg_fastq_index", "fxg_fastq_pack", "fxg_fastq_format", "fxg_fastq_format_opts", "fxg_fasta_weights", "fxg_host_register", "fxg_host_unregister",
     "fxg_shard_range", "fxg_epilogue", "fxg_concat_pwrite", "fxg_concat_peer", "fxg_device_count", "fxg_device_numa_node", "fxg_comm_create", "fxg_comm_destroy", "fxg_epilogue_rccl",
-    "fxg_barcode_prepare", "fxg_barcode_split", "fxg_fasta_reflow", "fxg_fasta_uncollapse",
+    "fxg_barcode_prepare", "fxg_barcode_split", "fxg_fasta_reflow", "fxg_fasta_uncollapse", "fxg_bases_change",
 ]
 
 
@@ -95,6 +95,13 @@ class FxgUncollapseInfo(C.Structure):
 
 
 UNCOLLAPSE_TEXT_MAX = 1 << 28    # FXG_UC_TEXT_MAX
+
+
+class FxgBasesChangeInfo(C.Structure):
+    _fields_ = [("changed", C.c_uint64), ("first_to_record", C.c_uint64), ("irregular", C.c_uint32)]
+
+
+NO_RECORD = (1 << 64) - 1        # fxg_bases_change_info.first_to_record: no record holds a `to` byte
 
 
 def reflow_bound(text_len):
@@ -194,6 +201,8 @@ def load_library(path=None):
         L.fxg_fasta_reflow.argtypes = [vp, vp, u64, i32, u64, C.POINTER(FxgReflowOpts), vp, u64, vp, C.POINTER(FxgReflowInfo)]
     if hasattr(L, "fxg_fasta_uncollapse"):   # (as above)
         L.fxg_fasta_uncollapse.argtypes = [vp, vp, u64, vp, u64, u64, vp, C.POINTER(FxgUncollapseOpts), vp, C.POINTER(FxgUncollapseInfo)]
+    if hasattr(L, "fxg_bases_change"):       # (as above)
+        L.fxg_bases_change.argtypes = [vp, vp, u64, i32, vp, u64, u64, i32, i32, C.POINTER(FxgBasesChangeInfo)]
     L.fxg_set_profiling.argtypes = [vp, i32]
     L.fxg_set_clip_history.argtypes = [vp, i32]
     L.fxg_run_quality_stats.argtypes = [vp, C.POINTER(FxgBatch), vp, C.c_uint32]
@@ -586,6 +595,18 @@ class Engine:
         self._check(self.lib.fxg_fasta_uncollapse(self.ctx, d_text.data_ptr(), text_len, ix.line.data_ptr(), ix.cap_lines, n, lens.data_ptr(), C.byref(o),
                                                   out.data_ptr() if out is not None else None, C.byref(info)))
         return (out[:info.out_bytes] if out is not None else None), info
+
+    def bases_change(self, d_text, text_len, ix, n, rna_to_dna=False):
+        """fasta_nucleotide_changer on an indexed block (fxg_bases_change in include/fxg.h): T -> U in the bases lines of d_text, in place, or
+        U -> T with rna_to_dna.  Returns the info: changed, first_to_record (NO_RECORD: none), irregular."""
+        if not hasattr(self.lib, "fxg_bases_change"):
+            raise FxgError("this libfxg.so has no fxg_bases_change")
+        frm, to = (ord("U"), ord("T")) if rna_to_dna else (ord("T"), ord("U"))
+        info = FxgBasesChangeInfo()
+        self._after_torch()
+        self._check(self.lib.fxg_bases_change(self.ctx, d_text.data_ptr(), text_len, ix.lpr, ix.line.data_ptr(), ix.cap_lines, n, frm, to, C.byref(info)))
+        self._before_torch()
+        return info
 
     def read_counters(self, d_counters):
         host = (C.c_uint64 * NCOUNTERS)()

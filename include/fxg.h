@@ -190,6 +190,9 @@ typedef struct fxg_out {
  *   fasta uncollapse (below) d_text: the bytes of the records' lines (text_len + 16 readable, as for the text path); d_line: 2 * cap_lines uint32,
  *                            read at entries 0 .. 2 * records - 1 of either half; d_len: read records uint16; d_out: write exactly
  *                            info->out_bytes bytes, never a byte past them, and none at all when the request is refused.
+ *   bases change (below)     d_text: read as for the text path (text_len + 16 bytes), written only inside the records' bases lines, from a
+ *                            line's start to its chomped end; d_line: 2 * cap_lines uint32, read at entries lines_per_record * r + 1 of
+ *                            either half.
  * tests/test_emu_bounds.py runs the kernels' bodies with every array against a guard page at these ends; tests/test_gpu_bounds.py surrounds every
  * array with poison (inputs) and canaries (outputs) on the device. */
 
@@ -414,6 +417,25 @@ typedef struct fxg_uncollapse_info {
 } fxg_uncollapse_info;
 int  fxg_fasta_uncollapse(fxg_ctx *ctx, const uint8_t *d_text, uint64_t text_len, const uint32_t *d_line, uint64_t cap_lines, uint64_t records,
                           const uint16_t *d_len, const fxg_uncollapse_opts *opts, uint8_t *d_out, fxg_uncollapse_info *info);
+/* fasta_nucleotide_changer (reference src/fasta_nucleotide_changer/fasta_nucleotide_changer.c:101-115): the bases lines of an indexed block
+ * rewritten in place.  The block has been through fxg_fastq_index (d_text, text_len, lines_per_record, d_line, cap_lines and records as that
+ * call was given and left them).  (from, to) is ('T', 'U') -- DNA to RNA, the tool's -r -- or ('U', 'T') -- RNA to DNA, -d.  The call walks
+ * the bases line of every record, line lines_per_record * r + 1 from its start to its chomped end: every `from` byte becomes `to` in
+ * d_text and is counted; the smallest record whose bases line holds a `to` byte is reported (the reference stops there with a message);
+ * a bases byte outside upper-case A C G T N U raises FXG_TEXT_IRR_BASE.  Every `from` byte of every record is rewritten whatever the other
+ * two results say.  Nothing but `from` bytes of bases lines is written: ids, '+' lines, quality lines, a CR before the newline, the
+ * newlines and the 16 bytes behind the text stay.  The block then goes out through fxg_fastq_format with out_fasta = 1, over
+ * first_to_record records when a `to` byte was found.
+ * Refused (FXG_E_INVALID with a message, nothing launched, info zeroed with first_to_record = ~0): another (from, to); lines_per_record not
+ * 2 or 4; a null d_text or d_line with records > 0; a null info; more records than cap_lines or text_len can hold.  records == 0 is a valid
+ * call that launches nothing.  The context needs no call before this one.  Synchronises.  With profiling on, a call records one interval. */
+typedef struct fxg_bases_change_info {
+    uint64_t changed;          /* `from` bytes rewritten, whole call */
+    uint64_t first_to_record;  /* smallest record index whose bases line holds a `to` byte; ~0ull: none */
+    uint32_t irregular;        /* FXG_TEXT_IRR_BASE if any bases byte is outside upper-case A C G T N U */
+} fxg_bases_change_info;
+int  fxg_bases_change(fxg_ctx *ctx, uint8_t *d_text, uint64_t text_len, int lines_per_record, const uint32_t *d_line, uint64_t cap_lines,
+                      uint64_t records, int from, int to, fxg_bases_change_info *info);
 int  fxg_host_register(fxg_ctx *ctx, void *ptr, size_t bytes);     /* page-lock an existing host buffer for async copies */
 int  fxg_host_unregister(fxg_ctx *ctx, void *ptr);
 
