@@ -8,6 +8,7 @@
 #include "fxg_reflow.h"
 #include "fxg_uncollapse.h"
 #include "fxg_nucchange.h"
+#include "fxg_collapse.h"
 
 extern "C" int fxg_abi_version(void) { return FXG_ABI_VERSION; }
 
@@ -43,6 +44,11 @@ extern "C" void fxg_ctx_destroy(fxg_ctx *c)
     (void)hipFree(c->text_ws); (void)hipFree(c->text_state); (void)hipFree(c->fb_blk);
     (void)hipFree(c->hist_buf[0]); (void)hipFree(c->hist_buf[1]); (void)hipFree(c->hist_w); (void)hipFree(c->hist_ws); (void)hipFree(c->stats_ws); (void)hipFree(c->clip_ck);
     (void)hipFree(c->bc_tab); (void)hipFree(c->bc_ws); (void)hipFree(c->rf_ws); (void)hipFree(c->uc_ws); (void)hipFree(c->nc_res);
+    if (c->cl) {
+        (void)hipFree(c->cl->arena); (void)hipFree(c->cl->off); (void)hipFree(c->cl->cnt); (void)hipFree(c->cl->len); (void)hipFree(c->cl->slots);
+        (void)hipFree(c->cl->tmp); (void)hipFree(c->cl->ord); (void)hipFree(c->cl->res);
+        free(c->cl);
+    }
     if (c->ev0) (void)hipEventDestroy(c->ev0);
     if (c->ev1) (void)hipEventDestroy(c->ev1);
     for (int i = 0; i < FXG_KEV_RING; ++i) { if (c->kev0[i]) (void)hipEventDestroy(c->kev0[i]); if (c->kev1[i]) (void)hipEventDestroy(c->kev1[i]); }
@@ -737,6 +743,93 @@ int fxg_bases_change(fxg_ctx *c, uint8_t *d_text, uint64_t text_len, int lines_p
     fxg_nc_results(res, info);
     fxg_note_launch(c, "fxg_kernel_bases_change", (u32)grid, FXG_BLOCK, 0, 0);
     return FXG_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// fastx_collapser (fxg_collapse.h): the set of a context -- copy + check, rebuild, insert per block; mark, scan, scatter, replay, sizes; windows
+// ------------------------------------------------------------------------------------------------
+// the backend of fxg_cl_begin / _add / _order / _write: the context's stream
+struct FxgClEngine {
+    fxg_ctx *c; char *err; size_t cap;
+    int alloc(void **p, u64 bytes, const char *what)
+    {
+        if (hipMalloc(p, bytes) == hipSuccess) return FXG_OK;
+        (void)hipGetLastError();
+        *p = nullptr;
+        return fxg_fail(c, FXG_E_NOMEM, "fxg_collapse: the set wanted %llu bytes for %s, and the device did not have them", (unsigned long long)bytes, what);
+    }
+    void release(void *p) { (void)hipStreamSynchronize(c->stream); (void)hipFree(p); }
+    int zero(void *p, u64 bytes) { FXG_HIP(c, hipMemsetAsync(p, 0, bytes, c->stream)); return FXG_OK; }
+    int copy(void *dst, const void *src, u64 bytes) { FXG_HIP(c, hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, c->stream)); return FXG_OK; }
+    int up(void *dst, const void *src, u64 bytes) { FXG_HIP(c, hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, c->stream)); return sync(); }
+    int down(void *dst, const void *src, u64 bytes) { FXG_HIP(c, hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, c->stream)); return sync(); }
+    int sync() { FXG_HIP(c, hipStreamSynchronize(c->stream)); return FXG_OK; }
+    int scan(u64 *data, u64 n, u64 *levels) { return fxg_scan_u64(c, data, n, levels); }
+    int lens(const uint16_t *dlen, u64 n, u64 *tmp) { FXG_LAUNCH(c, fxg_kernel_cl_lens, (u32)((n + FXG_BLOCK) / FXG_BLOCK), FXG_BLOCK, 0, dlen, n, tmp); return FXG_OK; }
+    int copy_check(const FxgClAddArgs &a) { FXG_LAUNCH(c, fxg_kernel_cl_copy, (u32)fxg_cl_grid(a.n * FXG_CL_LANES, FXG_CL_GRID_MAX), FXG_BLOCK, 0, a); return FXG_OK; }
+    int init(u64 *slots, u64 nslots) { FXG_LAUNCH(c, fxg_kernel_cl_init, (u32)fxg_cl_grid(nslots, FXG_CL_SLOT_GRID_MAX), FXG_BLOCK, 0, slots, nslots); return FXG_OK; }
+    int rebuild(const u64 *old, u64 nold, const FxgClSet &s, u32 hash_bits) { FXG_LAUNCH(c, fxg_kernel_cl_rebuild, (u32)fxg_cl_grid(nold, FXG_CL_SLOT_GRID_MAX), FXG_BLOCK, 0, old, nold, s, hash_bits); return FXG_OK; }
+    int insert(const FxgClSet &s, u64 rec0, u64 n, u32 hash_bits)
+    {
+        const u64 grid = (n + FXG_BLOCK - 1) / FXG_BLOCK;            // a block's records are fewer than 2^31 (its line index is 32 bits wide)
+        FXG_LAUNCH(c, fxg_kernel_cl_insert, (u32)grid, FXG_BLOCK, 0, s, rec0, n, hash_bits);
+        fxg_note_launch(c, "fxg_kernel_cl_insert", (u32)grid, FXG_BLOCK, FXG_CL_STAGE_BYTES, FXG_BLOCK);
+        return FXG_OK;
+    }
+    int mark(const FxgClSet &s, u64 *flags) { FXG_LAUNCH(c, fxg_kernel_cl_mark, (u32)fxg_cl_grid(s.nslots, FXG_CL_SLOT_GRID_MAX), FXG_BLOCK, 0, s, flags); return FXG_OK; }
+    int scatter(const FxgClOrd &o) { FXG_LAUNCH(c, fxg_kernel_cl_scatter, (u32)fxg_cl_grid(o.s.nslots, FXG_CL_SLOT_GRID_MAX), FXG_BLOCK, 0, o); return FXG_OK; }
+    int sizes(const FxgClOrd &o) { FXG_LAUNCH(c, fxg_kernel_cl_sizes, (u32)fxg_cl_grid(o.uniques + 1, FXG_CL_SLOT_GRID_MAX), FXG_BLOCK, 0, o); return FXG_OK; }
+    int window(const FxgClOrd &o, u64 rank_begin, u64 out_cap) { FXG_LAUNCH(c, fxg_kernel_cl_window, 1, 1, 0, o, rank_begin, out_cap); return FXG_OK; }
+    int write(const FxgClOrd &o, u64 rank_begin, u64 rank_end)
+    {
+        const u64 grid = ((rank_end - rank_begin) * FXG_CL_LANES + FXG_BLOCK - 1) / FXG_BLOCK;
+        FXG_LAUNCH(c, fxg_kernel_cl_write, (u32)grid, FXG_BLOCK, 0, o, rank_begin, rank_end);
+        fxg_note_launch(c, "fxg_kernel_cl_write", (u32)grid, FXG_BLOCK, 0, 0);
+        return FXG_OK;
+    }
+    void interval_begin() { if (c->profiling) (void)hipEventRecord(c->kev0[c->kev_count % FXG_KEV_RING], c->stream); }
+    void interval_end() { if (c->profiling) { (void)hipEventRecord(c->kev1[c->kev_count % FXG_KEV_RING], c->stream); c->kev_count++; } }
+};
+
+// (C linkage from their declarations in include/fxg.h, as fxg_bases_change above; their first calls on a new context are in tests/test_gpu_collapse.py.)
+int fxg_collapse_begin(fxg_ctx *c, const fxg_collapse_opts *opts)
+{
+    if (!c) return FXG_E_INVALID;
+    FXG_HIP(c, hipSetDevice(c->device));
+    if (!c->cl && !(c->cl = (FxgClState *)calloc(1, sizeof(FxgClState)))) return FXG_E_NOMEM;
+    FxgClEngine b = {c, c->err, sizeof c->err};
+    return fxg_cl_begin(b, *c->cl, opts);
+}
+
+// a context without a set: every call but begin is refused by the state's own checks
+static FxgClState *fxg_cl_state(fxg_ctx *c, FxgClState *none) { memset(none, 0, sizeof *none); return c->cl ? c->cl : none; }
+
+int fxg_collapse_add(fxg_ctx *c, const uint8_t *d_text, uint64_t text_len, int lines_per_record, const uint32_t *d_line, uint64_t cap_lines, uint64_t records,
+                     const uint16_t *d_len, fxg_collapse_info *info)
+{
+    if (!c) return FXG_E_INVALID;
+    FxgClState none;
+    FxgClEngine b = {c, c->err, sizeof c->err};
+    FXG_HIP(c, hipSetDevice(c->device));
+    return fxg_cl_add(b, *fxg_cl_state(c, &none), d_text, text_len, lines_per_record, d_line, cap_lines, records, d_len, info);
+}
+
+int fxg_collapse_order(fxg_ctx *c, fxg_collapse_info *info)
+{
+    if (!c) return FXG_E_INVALID;
+    FxgClState none;
+    FxgClEngine b = {c, c->err, sizeof c->err};
+    FXG_HIP(c, hipSetDevice(c->device));
+    return fxg_cl_order(b, *fxg_cl_state(c, &none), info);
+}
+
+int fxg_collapse_write(fxg_ctx *c, uint64_t rank_begin, uint64_t out_cap, uint8_t *d_out, fxg_collapse_window *window)
+{
+    if (!c) return FXG_E_INVALID;
+    FxgClState none;
+    FxgClEngine b = {c, c->err, sizeof c->err};
+    FXG_HIP(c, hipSetDevice(c->device));
+    return fxg_cl_write(b, *fxg_cl_state(c, &none), rank_begin, out_cap, d_out, window);
 }
 
 extern "C" int fxg_host_register(fxg_ctx *c, void *ptr, size_t bytes)

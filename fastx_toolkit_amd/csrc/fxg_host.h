@@ -20,6 +20,7 @@
 #include "fxg_rows.h"
 
 struct FxgTextState;
+struct FxgClState;
 
 struct fxg_ctx {
     int device;
@@ -78,6 +79,7 @@ struct fxg_ctx {
     u64 uc_records, uc_base;            // what the scans in uc_ws were made for (a call with copy_begin > 0 must name the same)
     int uc_ready;
     u64 *nc_res;                        // fxg_bases_change: the launch's result words (fxg_nucchange.h)
+    FxgClState *cl;                     // fxg_collapse_*: the set and what the host knows of it (fxg_collapse.h), made by the first fxg_collapse_begin
 };
 
 __attribute__((unused)) static int fxg_fail(fxg_ctx *ctx, int code, const char *fmt, ...)

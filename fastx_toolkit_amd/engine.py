@@ -27,6 +27,7 @@ EXPORTS = [
     "fxg_fastq_index", "fxg_fastq_pack", "fxg_fastq_format", "fxg_fastq_format_opts", "fxg_fasta_weights", "fxg_host_register", "fxg_host_unregister",
     "fxg_shard_range", "fxg_epilogue", "fxg_concat_pwrite", "fxg_concat_peer", "fxg_device_count", "fxg_device_numa_node", "fxg_comm_create", "fxg_comm_destroy", "fxg_epilogue_rccl",
     "fxg_barcode_prepare", "fxg_barcode_split", "fxg_fasta_reflow", "fxg_fasta_uncollapse", "fxg_bases_change",
+    "fxg_collapse_begin", "fxg_collapse_add", "fxg_collapse_order", "fxg_collapse_write",
 ]
 
 
@@ -101,7 +102,20 @@ class FxgBasesChangeInfo(C.Structure):
     _fields_ = [("changed", C.c_uint64), ("first_to_record", C.c_uint64), ("irregular", C.c_uint32)]
 
 
-NO_RECORD = (1 << 64) - 1        # fxg_bases_change_info.first_to_record: no record holds a `to` byte
+NO_RECORD = (1 << 64) - 1        # fxg_bases_change_info.first_to_record: no record holds a `to` byte; fxg_collapse_info.first_bad: the block is regular
+
+
+class FxgCollapseOpts(C.Structure):
+    _fields_ = [("initial_slots", C.c_uint64), ("hash_bits", C.c_uint32)]
+
+
+class FxgCollapseInfo(C.Structure):
+    _fields_ = [("records", C.c_uint64), ("reads", C.c_uint64), ("uniques", C.c_uint64), ("slots", C.c_uint64), ("rebuilds", C.c_uint64),
+                ("first_bad", C.c_uint64), ("out_reads", C.c_uint64), ("out_bytes", C.c_uint64), ("irregular", C.c_uint32)]
+
+
+class FxgCollapseWindow(C.Structure):
+    _fields_ = [("rank_end", C.c_uint64), ("out_bytes", C.c_uint64)]
 
 
 def reflow_bound(text_len):
@@ -203,6 +217,11 @@ def load_library(path=None):
         L.fxg_fasta_uncollapse.argtypes = [vp, vp, u64, vp, u64, u64, vp, C.POINTER(FxgUncollapseOpts), vp, C.POINTER(FxgUncollapseInfo)]
     if hasattr(L, "fxg_bases_change"):       # (as above)
         L.fxg_bases_change.argtypes = [vp, vp, u64, i32, vp, u64, u64, i32, i32, C.POINTER(FxgBasesChangeInfo)]
+    if hasattr(L, "fxg_collapse_begin"):     # (as above)
+        L.fxg_collapse_begin.argtypes = [vp, C.POINTER(FxgCollapseOpts)]
+        L.fxg_collapse_add.argtypes = [vp, vp, u64, i32, vp, u64, u64, vp, C.POINTER(FxgCollapseInfo)]
+        L.fxg_collapse_order.argtypes = [vp, C.POINTER(FxgCollapseInfo)]
+        L.fxg_collapse_write.argtypes = [vp, u64, u64, vp, C.POINTER(FxgCollapseWindow)]
     L.fxg_set_profiling.argtypes = [vp, i32]
     L.fxg_set_clip_history.argtypes = [vp, i32]
     L.fxg_run_quality_stats.argtypes = [vp, C.POINTER(FxgBatch), vp, C.c_uint32]
@@ -607,6 +626,39 @@ class Engine:
         self._check(self.lib.fxg_bases_change(self.ctx, d_text.data_ptr(), text_len, ix.lpr, ix.line.data_ptr(), ix.cap_lines, n, frm, to, C.byref(info)))
         self._before_torch()
         return info
+
+    def collapse_begin(self, initial_slots=0, hash_bits=0):
+        """fastx_collapser: empties the context's set of sequences (fxg_collapse_begin in include/fxg.h).  Both arguments are test and
+        measurement aids that never change a result."""
+        if not hasattr(self.lib, "fxg_collapse_begin"):
+            raise FxgError("this libfxg.so has no fxg_collapse_begin")
+        o = FxgCollapseOpts(initial_slots, hash_bits)
+        self._check(self.lib.fxg_collapse_begin(self.ctx, C.byref(o)))
+
+    def collapse_add(self, d_text, text_len, ix, n, lens):
+        """One indexed block (fastq_index) into the set, in input order.  Returns the info: the set's records, reads, uniques, slots and rebuilds
+        so far; irregular != 0 (first_bad: the block's first such record) means nothing of the block went in."""
+        info = FxgCollapseInfo()
+        self._after_torch()
+        self._check(self.lib.fxg_collapse_add(self.ctx, d_text.data_ptr() if d_text is not None else None, text_len, ix.lpr, ix.line.data_ptr(), ix.cap_lines, n,
+                                              lens.data_ptr() if lens is not None else None, C.byref(info)))
+        return info
+
+    def collapse_order(self):
+        """After the last block: the set numbered and ordered as the reference's output is.  Returns the info; out_bytes is the whole output."""
+        info = FxgCollapseInfo()
+        self._check(self.lib.fxg_collapse_order(self.ctx, C.byref(info)))
+        return info
+
+    def collapse_write(self, rank_begin, out, out_cap=None):
+        """The longest run of whole records from rank_begin on that fits out (or out_cap bytes of it).  Returns (view, window): the view holds
+        exactly the bytes written, window.rank_end is the next call's rank_begin until it equals the set's uniques."""
+        cap = (out.numel() if out is not None else 0) if out_cap is None else out_cap
+        w = FxgCollapseWindow()
+        self._after_torch()
+        self._check(self.lib.fxg_collapse_write(self.ctx, rank_begin, cap, out.data_ptr() if out is not None else None, C.byref(w)))
+        self._before_torch()
+        return (out[:w.out_bytes] if out is not None else None), w
 
     def read_counters(self, d_counters):
         host = (C.c_uint64 * NCOUNTERS)()

@@ -436,6 +436,64 @@ typedef struct fxg_bases_change_info {
 } fxg_bases_change_info;
 int  fxg_bases_change(fxg_ctx *ctx, uint8_t *d_text, uint64_t text_len, int lines_per_record, const uint32_t *d_line, uint64_t cap_lines,
                       uint64_t records, int from, int to, fxg_bases_change_info *info);
+/* fastx_collapser (reference src/fastx_collapser/fastx_collapser.cpp:112-122): identical reads merged on the device.  A context holds one
+ * set of sequences across blocks:
+ *   fxg_collapse_begin   empties the set (device memory of an earlier set is kept and reused);
+ *   fxg_collapse_add     one block that has been through fxg_fastq_index (d_text, text_len, lines_per_record, d_line, cap_lines, records and
+ *                        d_len as that call was given and left them): the bases line of every record is checked against upper-case A C G T N,
+ *                        copied into the set's arena and inserted, with the record's read count -- 1 for FASTQ, the number after the first
+ *                        '-' of a FASTA id as atoi reads it, 1 if there is none or it is not positive (fastx.c:475-495).  Counts add up modulo
+ *                        2^64.  A byte outside the alphabet, an empty bases line or a d_len entry that is not its line's length makes the
+ *                        block irregular: info->irregular = FXG_TEXT_IRR_BASE, info->first_bad the smallest such record of the block, and
+ *                        NOTHING of the block stays in the set -- the call returns FXG_OK and the set is what it was.  Blocks are added in
+ *                        input order: the order of equal counts in the output depends on it.  Synchronises.
+ *   fxg_collapse_order   after the last block: numbers the distinct sequences in first-occurrence order, downloads 16 bytes per distinct
+ *                        sequence (hash and count), replays the reference's container on the host -- a std::unordered_map filled in that
+ *                        order, iterated, stable-sorted by count, read backwards -- and sizes the output.  The result is byte-identical to the
+ *                        reference built with HAVE_CXX11 == 1 against the libstdc++ this library was built with: records in descending count
+ *                        order, equal counts in the reverse of that map's iteration order.  info->out_bytes is the whole output,
+ *                        info->out_reads the second number of the reference's -v report (see below).
+ *   fxg_collapse_write   the longest run of WHOLE records from rank_begin on that fits out_cap bytes, ranks [rank_begin, window->rank_end),
+ *                        window->out_bytes bytes from d_out[0] on: ">rank-count\nBASES\n" with rank counted from 1.  The reference prints a
+ *                        count after truncation to int (a sum of 2^31 prints as -2147483648, one of 2^32 as 0) and adds those ints into the
+ *                        size_t of its report; both are reproduced, the sort uses the untruncated sums.  Exactly out_bytes bytes are written,
+ *                        never a byte past them.  rank_begin == uniques is a valid call that writes nothing.  Synchronises.
+ * Refused (FXG_E_INVALID with a message, nothing launched, d_out untouched): add, order or write before begin; add or order after order; write
+ * before order; more than 2^40 - 2 records in a set; a null pointer with records > 0; lines_per_record other than 2 or 4; more records than
+ * cap_lines or text_len can hold, text_len above 0xFFFFFFF0; rank_begin above uniques; an out_cap smaller than record rank_begin (the message
+ * says how many bytes it needs).  A device allocation that fails is FXG_E_NOMEM and says how many bytes the set wanted; the set is then as it
+ * was before the call.
+ * The set is resident: its device memory is about the bases + 18 bytes per record + 48 to 96 bytes per distinct sequence (a table that is at
+ * most half full), and fxg_collapse_order needs 8 more per record and 40 per distinct sequence while it runs; the host replay takes about 48
+ * bytes per distinct sequence.  With profiling on, add records an interval for lengths + scan + copy + check, one for a rebuild of the table
+ * if the block caused one, and one for the insert; order records two (mark + scan + scatter; sizes + scan), write one. */
+typedef struct fxg_collapse_opts {
+    /* Both fields are test and measurement aids: they never change a result.  A null opts is {0, 0}. */
+    uint64_t initial_slots;  /* slots of the table at first, rounded up to a power of two, 4 at the least; 0: the default, 65 536.  The table
+                              * is rebuilt at twice the size or more whenever a block could fill it beyond a half. */
+    uint32_t hash_bits;      /* 0: all 64.  k: only the low k bits of a sequence's hash reach the slot index and the fingerprint, so k = 1 puts
+                              * every key on two probe chains and makes every probe compare bytes.  The order still uses the whole hash. */
+} fxg_collapse_opts;
+typedef struct fxg_collapse_info {
+    uint64_t records;        /* in the set */
+    uint64_t reads;          /* their counts together */
+    uint64_t uniques;        /* distinct sequences */
+    uint64_t slots;          /* of the table */
+    uint64_t rebuilds;       /* of the table since begin */
+    uint64_t first_bad;      /* add: the smallest irregular record of the block, ~0ull if none */
+    uint64_t out_reads;      /* order: the printed (int) counts added into a size_t, the reference's "representing N reads" of its Output line */
+    uint64_t out_bytes;      /* order: bytes of the whole output */
+    uint32_t irregular;      /* add: FXG_TEXT_IRR_BASE if the block was refused as irregular */
+} fxg_collapse_info;
+typedef struct fxg_collapse_window {
+    uint64_t rank_end;       /* this call wrote ranks [rank_begin, rank_end) */
+    uint64_t out_bytes;      /* written to d_out */
+} fxg_collapse_window;
+int  fxg_collapse_begin(fxg_ctx *ctx, const fxg_collapse_opts *opts);
+int  fxg_collapse_add(fxg_ctx *ctx, const uint8_t *d_text, uint64_t text_len, int lines_per_record, const uint32_t *d_line, uint64_t cap_lines,
+                      uint64_t records, const uint16_t *d_len, fxg_collapse_info *info);
+int  fxg_collapse_order(fxg_ctx *ctx, fxg_collapse_info *info);
+int  fxg_collapse_write(fxg_ctx *ctx, uint64_t rank_begin, uint64_t out_cap, uint8_t *d_out, fxg_collapse_window *window);
 int  fxg_host_register(fxg_ctx *ctx, void *ptr, size_t bytes);     /* page-lock an existing host buffer for async copies */
 int  fxg_host_unregister(fxg_ctx *ctx, void *ptr);
 
