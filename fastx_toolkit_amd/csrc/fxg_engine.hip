@@ -720,8 +720,8 @@ extern "C" int fxg_fasta_uncollapse(fxg_ctx *c, const uint8_t *d_text, uint64_t 
 // ------------------------------------------------------------------------------------------------
 // fasta_nucleotide_changer (fxg_nucchange.h): one launch, groups of 16 lanes that take a record at a time
 // ------------------------------------------------------------------------------------------------
-// (C linkage from its declaration in include/fxg.h.  The table of first calls in tests/context_state_cases.py lists the definitions above; this
-// entry's first call on a new context is in tests/test_gpu_nucchange.py.)
+// (C linkage from its declaration in include/fxg.h.  Its rows in the table of first calls, tests/context_state_cases.py: bases_change_other_contexts_lines,
+// bases_change_no_records.)
 int fxg_bases_change(fxg_ctx *c, uint8_t *d_text, uint64_t text_len, int lines_per_record, const uint32_t *d_line, uint64_t cap_lines, uint64_t records,
                      int from, int to, fxg_bases_change_info *info)
 {
@@ -791,7 +791,7 @@ struct FxgClEngine {
     void interval_end() { if (c->profiling) { (void)hipEventRecord(c->kev1[c->kev_count % FXG_KEV_RING], c->stream); c->kev_count++; } }
 };
 
-// (C linkage from their declarations in include/fxg.h, as fxg_bases_change above; their first calls on a new context are in tests/test_gpu_collapse.py.)
+// (C linkage from their declarations in include/fxg.h, as fxg_bases_change above.  Their rows in the table of first calls, tests/context_state_cases.py: collapse_*.)
 int fxg_collapse_begin(fxg_ctx *c, const fxg_collapse_opts *opts)
 {
     if (!c) return FXG_E_INVALID;

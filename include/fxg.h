@@ -462,7 +462,9 @@ int  fxg_bases_change(fxg_ctx *ctx, uint8_t *d_text, uint64_t text_len, int line
  * before order; more than 2^40 - 2 records in a set; a null pointer with records > 0; lines_per_record other than 2 or 4; more records than
  * cap_lines or text_len can hold, text_len above 0xFFFFFFF0; rank_begin above uniques; an out_cap smaller than record rank_begin (the message
  * says how many bytes it needs).  A device allocation that fails is FXG_E_NOMEM and says how many bytes the set wanted; the set is then as it
- * was before the call.
+ * was before the call.  What a refused call leaves in its results: add and order refused for the set's state (no set, or an ordered one) leave
+ * *info zeroed with first_bad = ~0ull; add refused for its arguments leaves the set's counts as they are (records, reads, uniques, slots,
+ * rebuilds), irregular = 0 and first_bad = ~0ull; a refused write leaves *window zeroed with rank_end = rank_begin.
  * The set is resident: its device memory is about the bases + 18 bytes per record + 48 to 96 bytes per distinct sequence (a table that is at
  * most half full), and fxg_collapse_order needs 8 more per record and 40 per distinct sequence while it runs; the host replay takes about 48
  * bytes per distinct sequence.  With profiling on, add records an interval for lengths + scan + copy + check, one for a rebuild of the table

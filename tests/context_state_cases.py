@@ -70,7 +70,20 @@ FIRST_CALLS = [
     ("fasta_uncollapse_continue_nothing", "fxg_fasta_uncollapse",
      refusal("fxg_fasta_uncollapse: copy_begin > 0 continues a block, and the context holds no scans of 5 records numbered from 8 on")),
     ("clip_history_then_batch", "fxg_set_clip_history", OK),
+    ("bases_change_other_contexts_lines", "fxg_bases_change", OK),
+    ("bases_change_no_records", "fxg_bases_change", OK),
+    ("collapse_begin", "fxg_collapse_begin", OK),
+    ("collapse_add_no_set", "fxg_collapse_add", refusal("fxg_collapse_add: no set; fxg_collapse_begin makes one", device=False)),
+    ("collapse_order_no_set", "fxg_collapse_order", refusal("fxg_collapse_order: no set; fxg_collapse_begin makes one", device=False)),
+    ("collapse_write_no_set", "fxg_collapse_write", refusal("fxg_collapse_write: no set; fxg_collapse_begin makes one", device=False)),
+    ("collapse_add_other_contexts_lines", "fxg_collapse_add", OK),                # (the first call after begin, on line arrays another context made)
 ]
+
+
+# What a refused collapser call leaves in its results (include/fxg.h): a call refused for the set's state leaves *info zeroed with first_bad = ~0, a
+# refused write leaves *window zeroed with rank_end = rank_begin; d_out is untouched.
+COLLAPSE_INFO_FIELDS = ("records", "reads", "uniques", "slots", "rebuilds", "first_bad", "out_reads", "out_bytes", "irregular")
+COLLAPSE_INFO_REFUSED = (0, 0, 0, 0, 0, (1 << 64) - 1, 0, 0, 0)
 
 
 # ---- the 43 tile kernels ---------------------------------------------------------------------------------------------------------------

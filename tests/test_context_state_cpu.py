@@ -27,17 +27,37 @@ def _no_knobs(monkeypatch):
         monkeypatch.delenv(k, raising=False)
 
 
-def engine_entry_points():
-    """the extern "C" functions of csrc/fxg_engine.hip whose first parameter is a context"""
-    src = open(os.path.join(ROOT, "fastx_toolkit_amd", "csrc", "fxg_engine.hip")).read()
+CSRC = os.path.join(ROOT, "fastx_toolkit_amd", "csrc")
+
+
+def spelled_extern_c():
+    """the functions of csrc/fxg_engine.hip that spell extern "C" at their definition and take a context first (what this table was held against before
+    the entries that take their linkage from include/fxg.h)"""
+    src = open(os.path.join(CSRC, "fxg_engine.hip")).read()
     return sorted(set(re.findall(r'^extern "C" [^\n(]*?\b(fxg_[a-z0-9_]+)\((?:const )?fxg_ctx \*', src, re.M)))
 
 
+def engine_entry_points():
+    """the functions include/fxg.h declares with a context as their first parameter that csrc/fxg_engine.hip or fxg_engine_clip.hip defines, whatever the
+    definition's spelling of linkage: at the start of a line, with or without extern "C", a body and no semicolon before it"""
+    hdr = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "fxg.h")).read(), flags=re.S)
+    declared = set(re.findall(r"\b(fxg_[a-z0-9_]+)\s*\(\s*(?:const\s+)?fxg_ctx\s*\*", hdr))
+    srcs = [open(os.path.join(CSRC, f)).read() for f in ("fxg_engine.hip", "fxg_engine_clip.hip")]
+
+    def defined(name):
+        pat = re.compile(r"^(?![ \t/#*])[^\n;=]*\b%s\((?:const )?fxg_ctx \*[^;{]*\{" % name, re.M)
+        return any(pat.search(s) for s in srcs)
+    return sorted(n for n in declared if defined(n))
+
+
 def test_first_call_table_has_every_entry_point():
+    spelled = spelled_extern_c()
+    assert set(spelled) - set(EXPORTS) == {"fxg_debug_phase_clocks"}          # (only the ablation builds have it: #ifdef FXG_ABLATION, not in include/fxg.h)
     entries = engine_entry_points()
-    assert set(entries) - set(EXPORTS) == {"fxg_debug_phase_clocks"}          # (only the ablation builds have it: #ifdef FXG_ABLATION, not in include/fxg.h)
-    entries = [e for e in entries if e in EXPORTS]
-    assert len(entries) >= 38
+    assert {e for e in spelled if e in EXPORTS} <= set(entries)               # what the table was held against before: reading the header can only add names
+    assert set(entries) <= set(EXPORTS)
+    assert len(entries) >= 44
+    assert {"fxg_bases_change", "fxg_collapse_begin", "fxg_collapse_add", "fxg_collapse_order", "fxg_collapse_write"} <= set(entries)      # (no extern "C" at their definitions)
     rows = {entry for _, entry, _ in K.FIRST_CALLS}
     assert rows == set(entries), (sorted(set(entries) - rows), sorted(rows - set(entries)))
     ids = [i for i, _, _ in K.FIRST_CALLS]
@@ -45,25 +65,68 @@ def test_first_call_table_has_every_entry_point():
     # the entry points the issue names as families, each present under the form it asks for
     for want in ("run_rows", "run_tiles", "run_clip", "quality_stats", "read_counters_zeroed", "fastq_index", "fastq_pack_other_contexts_lines", "fastq_format_opts_len_no_res",
                  "fasta_weights_unindexed", "barcode_split_without_prepare", "fasta_reflow", "fasta_reflow_empty_closes_record", "fasta_uncollapse_from_zero",
-                 "fasta_uncollapse_continue_nothing", "clip_history_then_batch"):
+                 "fasta_uncollapse_continue_nothing", "clip_history_then_batch",
+                 "bases_change_other_contexts_lines", "bases_change_no_records", "collapse_begin", "collapse_add_no_set", "collapse_order_no_set", "collapse_write_no_set",
+                 "collapse_add_other_contexts_lines"):
         assert want in ids
 
 
-def test_refusals_that_need_no_device_on_the_stub():
-    """a new context of the stub, the refused call its first: the code and the text of the table"""
+def collapse_stub_dir(tmp):
+    """a libfxg.so of the objects of emu_py.build_fmtopts (the stub and the entries request_cases.Session declares) plus the four collapser entries
+    (emu/collapse_stub.cpp over collapse_emu.cpp, as tests/test_collapse_cpu.py links them)"""
+    stock, fmt = emu.build_stub(), emu.build_fmtopts()
+    objs = [os.path.join(fmt, f + ".o") for f in ("fmtopts_stub", "bcsplit_stub", "bcsplit_emu")]
+    for f in ("collapse_emu", "collapse_stub"):
+        objs.append(os.path.join(tmp, f + ".o"))
+        subprocess.check_call(emu._CXX + ["-c", os.path.join(ROOT, "tests", "emu", f + ".cpp"), "-o", objs[-1]])
+    d = os.path.join(tmp, "stub")
+    os.makedirs(d)
+    subprocess.check_call(emu._LINK + [os.path.join(stock, "fxg_stub.o")] + objs + emu._emu_objects([]) + ["-o", os.path.join(d, "libfxg.so"), "-ldl"])
+    return d
+
+
+def test_refusals_that_need_no_device_on_the_stub(tmp_path):
+    """a new context of the stub, the refused call its first: the code and the text of the table, every output as include/fxg.h leaves it"""
     import ctypes as C
     import request_cases as R
-    rows = [(i, e, o) for i, e, o in K.FIRST_CALLS if o != K.OK and not o[3]]
-    assert [i for i, _, _ in rows] == ["barcode_split_without_prepare"]
+    from fastx_toolkit_amd.engine import FxgCollapseInfo, FxgCollapseWindow
+    rows = {i: o for i, e, o in K.FIRST_CALLS if o != K.OK and not o[3]}
+    assert sorted(rows) == ["barcode_split_without_prepare", "collapse_add_no_set", "collapse_order_no_set", "collapse_write_no_set"]
     s = R.Session(os.path.join(emu.build_fmtopts(), "libfxg.so"))
     try:
         out = (C.c_uint8 * 64)(*([0xA5] * 64))
         args = (s.p, 64, 4, s.p, 9, 2, None, C.addressof(out), s.bin_bytes, s.bin_records)
         rc = s.lib.fxg_barcode_split(s.ctx, *args)
-        assert (rc, s.last_error()) == (rows[0][2][1], rows[0][2][2])
+        assert (rc, s.last_error()) == rows["barcode_split_without_prepare"][1:3]
         assert bytes(out) == b"\xa5" * 64 and list(s.bin_bytes) == [0, 0]
     finally:
         s.close()
+    lib = os.path.join(collapse_stub_dir(str(tmp_path)), "libfxg.so")
+    vp, u64 = C.c_void_p, C.c_uint64
+    for cid in ("collapse_add_no_set", "collapse_order_no_set", "collapse_write_no_set"):          # each on a context of its own: its very first call
+        s = R.Session(lib)
+        try:
+            L = s.lib
+            L.fxg_collapse_add.argtypes = [vp, vp, u64, C.c_int, vp, u64, u64, vp, C.POINTER(FxgCollapseInfo)]
+            L.fxg_collapse_order.argtypes = [vp, C.POINTER(FxgCollapseInfo)]
+            L.fxg_collapse_write.argtypes = [vp, u64, u64, vp, C.POINTER(FxgCollapseWindow)]
+            info, win = FxgCollapseInfo(), FxgCollapseWindow(77, 77)
+            C.memset(C.byref(info), 0xEE, C.sizeof(info))
+            out = (C.c_uint8 * 64)(*([0xA5] * 64))
+            if cid == "collapse_add_no_set":
+                rc = L.fxg_collapse_add(s.ctx, s.p, 64, 2, s.p, 9, 2, s.p, C.byref(info))
+            elif cid == "collapse_order_no_set":
+                rc = L.fxg_collapse_order(s.ctx, C.byref(info))
+            else:
+                rc = L.fxg_collapse_write(s.ctx, 3, 64, C.addressof(out), C.byref(win))
+            assert (rc, s.last_error()) == rows[cid][1:3], cid
+            assert bytes(out) == b"\xa5" * 64, cid
+            if cid == "collapse_write_no_set":
+                assert (win.rank_end, win.out_bytes) == (3, 0), cid               # zeroed, rank_end = rank_begin
+            else:
+                assert tuple(getattr(info, k) for k in K.COLLAPSE_INFO_FIELDS) == K.COLLAPSE_INFO_REFUSED, cid
+        finally:
+            s.close()
 
 
 # ---- the attribute invariant ----------------------------------------------------------------------------------------------------------------

@@ -4,7 +4,8 @@ sizes and contexts.  Every comparison is exact, against the oracle, reflow_model
 outputs sit between canaries, text inputs before poison; every compacting run asserts scan_recoveries() unchanged.
 
   a  the first call a new context sees, for every entry point that takes a context (context_state_cases.FIRST_CALLS): 0 and the reference's answer, or the
-     documented refusal with its code, its text and untouched outputs
+     documented refusal with its code, its text and untouched outputs (the collapser's four entries and fxg_bases_change among them; the set among the
+     other families is tests/test_gpu_context_state_collapse.py)
   b  one context, about 150 calls of all families interleaved (context_state_sequence.py), every workspace reallocated at least twice while another
      family's kept data must survive; fb_blk on a context whose launches are all done again without the scanner
   c  one context through all 43 tile kernels, then kernels alternating between two LDS sizes, two contexts alternating, two threads with a context each
@@ -67,8 +68,21 @@ def collapsed_block(n, salt):
     return cached(("collapsed", n, salt), make)
 
 
+def fasta_block(n):
+    """n two-line records of 20 to 28 bases of collapse_cases.seq (every letter of ACGTN), ids of every width modulo 16"""
+    def make():
+        import collapse_cases as CK
+        records = [(CK.ident(i), CK.seq(i, 20 + i % 9)) for i in range(n)]
+        return dict(kind="fasta", lpr=2, text=b"".join(b">" + a + b"\n" + b + b"\n" for a, b in records), n=n, records=records, qual=None,
+                    lens=np.array([len(b) for _, b in records], np.uint16))
+    return cached(("fasta", n), make)
+
+
 def block_of(key):
-    return fastq_block(key[1]) if key[0] == "fastq" else collapsed_block(key[1], key[2])
+    if key[0] == "wide":                                      # (the unrelated blocks of collapse_state_sequence.py)
+        import collapse_state_sequence as Q
+        return Q.wide_block(key[1], key[2])
+    return fastq_block(key[1]) if key[0] == "fastq" else fasta_block(key[1]) if key[0] == "fasta" else collapsed_block(key[1], key[2])
 
 
 def line_marks(text, lines):
@@ -420,7 +434,7 @@ def _st(kind, label="first", **kw):
     return dict(kind=kind, label=label, **kw)
 
 
-SMALL_FASTQ, SMALL_COLLAPSED = ("fastq", 3000), ("collapsed", 3000, 1)
+SMALL_FASTQ, SMALL_COLLAPSED, SMALL_FASTA = ("fastq", 3000), ("collapsed", 3000, 1), ("fasta", 3000)
 
 
 def first_call(cid, outcome, fresh, other, mp):
@@ -575,6 +589,61 @@ def first_call(cid, outcome, fresh, other, mp):
         fresh.do_run(S._run("clip13", 3000, "first.batch1", ragged=True))
         fresh.do_run(S._run("clip13", 2000, "first.batch2", ragged=True))
         fresh.do_history(_st("history", on=False))
+    elif cid in ("bases_change_other_contexts_lines", "bases_change_no_records"):
+        import nucchange_model as NM
+        from fastx_toolkit_amd.engine import NO_RECORD, FxgBasesChangeInfo
+        x = other.do_index(_st("index", block=SMALL_FASTA))
+        other.eng.sync()
+        blk = NM.Block(x["blk"]["records"], "r")
+        none = cid == "bases_change_no_records"
+        info = FxgBasesChangeInfo(5, 5, 5)
+        eng._after_torch()
+        rc = lib.fxg_bases_change(eng.ctx, x["d_text"].data_ptr(), x["text_len"], 2, x["ix"].line.data_ptr(), x["ix"].cap_lines, 0 if none else x["n"], ord("T"), ord("U"), C.byref(info))
+        assert rc == 0, last_error(eng)
+        assert (info.changed, info.first_to_record, info.irregular) == ((0, NO_RECORD, 0) if none else (blk.changed, blk.first_to, blk.irregular))
+        host = x["d_text"].cpu().numpy()
+        assert host[:x["text_len"]].tobytes() == (blk.text if none else blk.rewritten) and (host[x["text_len"]:] == POISON).all()
+        assert blk.changed > 0 and blk.first_to == NO_RECORD and eng.last_launch()["kernel"] == ("" if none else "fxg_kernel_bases_change")
+    elif cid in ("collapse_begin", "collapse_add_other_contexts_lines"):
+        import collapse_cases as CK
+        import test_gpu_collapse as GC
+        records = [c for c in CK.abi_cases() if c[0] == "ties"][0][1]
+        assert GC.begin(eng) == 0, last_error(eng)
+        if cid == "collapse_begin":
+            out, _ = GC.run_blocks(eng, CK.split(records, 2))          # (begin once more, then the case: the first begin left a set that takes it)
+        else:
+            ix = GC.Indexed(other.eng, records)
+            other.eng.sync()
+            rc, info = GC.add(eng, ix)
+            want = GC.expected_info([records], False, 0)
+            assert rc == 0 and (info.records, info.reads, info.uniques, info.irregular) == (want["records"], want["reads"], want["uniques"], 0), last_error(eng)
+            rc, info = GC.order(eng)
+            assert rc == 0 and {k: getattr(info, k) for k in want} == want, last_error(eng)
+            _, out, w = GC.write(eng, 0, info.out_bytes)
+            assert w.rank_end == info.uniques
+        CK.assert_output("ties", out)
+    elif cid in ("collapse_add_no_set", "collapse_order_no_set", "collapse_write_no_set"):
+        import collapse_cases as CK
+        import test_gpu_collapse as GC
+        from fastx_toolkit_amd.engine import FxgCollapseInfo, FxgCollapseWindow
+        ix = GC.Indexed(other.eng, [(CK.ident(i), CK.seq(i, 20)) for i in range(10)])
+        other.eng.sync()
+        info, win = FxgCollapseInfo(), FxgCollapseWindow(77, 77)
+        C.memset(C.byref(info), 0xEE, C.sizeof(info))
+        out = fresh.g.alloc(256, fill=CANARY)
+        eng._after_torch()
+        if cid == "collapse_add_no_set":
+            rc = lib.fxg_collapse_add(eng.ctx, ix.d_text.data_ptr(), ix.text_len, 2, ix.ix.line.data_ptr(), ix.ix.cap_lines, ix.n, ix.lens.data_ptr(), C.byref(info))
+        elif cid == "collapse_order_no_set":
+            rc = lib.fxg_collapse_order(eng.ctx, C.byref(info))
+        else:
+            rc = lib.fxg_collapse_write(eng.ctx, 3, 256, out.data_ptr(), C.byref(win))
+        if cid == "collapse_write_no_set":                   # what include/fxg.h says a refused call leaves: the window zeroed with rank_end = rank_begin,
+            quiet = (win.rank_end, win.out_bytes) == (3, 0)
+        else:                                                 # info zeroed with first_bad = ~0
+            quiet = tuple(getattr(info, k) for k in K.COLLAPSE_INFO_FIELDS) == K.COLLAPSE_INFO_REFUSED
+        expect_refusal(eng, outcome, rc, bool((out == CANARY).all()) and quiet)
+        assert eng.last_launch()["kernel"] == ""                 # nothing launched
     else:
         raise AssertionError("no first call for " + cid)
     if outcome == K.OK:
