@@ -18,6 +18,13 @@
 //              of at least twice the size -- all keys differ, so a hash of the representative and a swap, no byte compare;
 //   insert     a launch of its own, after the copy: a workgroup takes 256 records, stages their span of the arena in LDS with 16-byte loads
 //              (when it fits FXG_CL_STAGE_BYTES; else the hash reads the arena), a lane hashes its record from there and probes.
+// A block of packed rows (fxg_collapse_add_rows: what fxg_run_pipeline compacts, record k = rlen[k] bytes at bases + roff[k]) takes the same road
+// with launches of its own in place of lens and copy+check: row lens, a lane to a row, the bytes the row gives (all of them, or the window
+// [first_base, last_base] of fastx_trimmer -f / -l; a row that ends before first_base gives none and gets no record number) and a flag, both
+// scanned: the rows' arena offsets and record numbers; copy rows, 16 lanes to a record as above, no alphabet check (the pack made it), a length
+// of zero raises the irregular word; counts, a lane to a record, the read count of the id line of source record kept[k] or 1.  They write only
+// arena bytes and off / len / cnt entries behind the set's end and reduce into the result words as copy+check does; the insert launch follows
+// as it is.
 // Coherence, the property to keep: the only words two workgroups share inside a launch are slot words, and those are touched by agent-scope
 // atomics only -- relaxed atomic loads for the probes, one compare-and-swap of `key` to claim an empty slot (a failed swap examines the value it
 // got back: the same slot again), atomic add on `count`, atomic min on `first`.  Every arena byte and every off / len / cnt entry a lane reads
@@ -67,6 +74,20 @@ struct FxgClAddArgs {
     u64 n; u32 lpr;
     const u64 *scan;                  // exclusive scan of dlen: the block's byte offsets
     u64 rec0, off0;                   // records and arena bytes before the block
+    FxgClSet s;
+};
+struct FxgClRowsArgs {
+    const uint8_t *bases;             // the caller's packed rows: record k is len(k) bytes at bases + roff[k], any alignment
+    const u64 *roff;
+    const uint16_t *rlen;
+    u32 first, last;                  // the window of a row that goes in: bases first .. last counted from 1; last == 0: to the row's end
+    const u32 *kept;                  // null: every record counts 1; else the source record of record k in the indexed FASTA text below
+    const uint8_t *text;
+    const u32 *ls, *le;
+    u64 n;
+    const u64 *scan;                  // exclusive scan of the bytes the rows give, n + 1 entries
+    const u64 *num;                   // exclusive scan of the rows' flags, n + 1 entries: row k is record rec0 + num[k] if num[k + 1] > num[k]
+    u64 rec0, off0;
     FxgClSet s;
 };
 struct FxgClOrd {
@@ -203,6 +224,51 @@ FXG_HD bool fxg_cl_copy_record(const FxgClAddArgs &a, u64 r, u32 l, u64 *count)
         *count = c;
     }
     return bad != 0u;
+}
+
+// ---- row lens, copy rows, counts (fxg_collapse_add_rows) ----
+// the bytes of a row of `len` that go in, from *start on: the trimmer's rule (fastx_trimmer.c:122-134), 0 if the row ends before `first`
+FXG_HD u32 fxg_cl_row_take(u32 len, u32 first, u32 last, u32 *start)
+{
+    *start = 0u;
+    if (last != 0u && last < len) len = last;
+    if (first > 1u) {
+        if (len < first) return 0u;
+        *start = first - 1u; len -= *start;
+    }
+    return len;
+}
+// entry r of the two arrays to scan (entry n closes them)
+FXG_HD void fxg_cl_row_len(const uint16_t *rlen, u64 n, u32 first, u32 last, u64 r, u64 *bytes, u64 *num)
+{
+    u32 start;
+    const u32 take = r < n ? fxg_cl_row_take(rlen[r], first, last, &start) : 0u;
+    bytes[r] = take; num[r] = take != 0u ? 1ull : 0ull;
+}
+// row r of the block by lane l of its group: its share of the copy, lane 0 writes the record's offset and length.  The byte count is the
+// scanned one, so the rows of a block fill exactly the bytes the host made room for.  Returns true if the row is empty (every lane of the
+// group agrees).
+FXG_HD bool fxg_cl_copy_row(const FxgClRowsArgs &a, u64 r, u32 l)
+{
+    const u32 len = a.rlen[r];
+    if (len == 0u) return true;
+    const u64 at = a.scan[r], take = a.scan[r + 1ull] - at, dst = a.off0 + at;
+    if (take == 0ull) return false;                              // ends before the window: not a record
+    u32 start;
+    (void)fxg_cl_row_take(len, a.first, a.last, &start);
+    fxg_bc_copy(a.s.arena + dst, a.bases + a.roff[r] + start, take, l, FXG_CL_LANES);
+    if (l == 0u) { const u64 g = a.rec0 + a.num[r]; a.s.off[g] = dst; a.s.len[g] = (uint16_t)take; }
+    return false;
+}
+// the read count of row r: that of the id line of its source record (get_reads_count, fastx.c:475-495), 1 without a count source; 0 if the
+// row is not a record
+FXG_HD u64 fxg_cl_row_count(const FxgClRowsArgs &a, u64 r)
+{
+    if (a.num[r + 1ull] == a.num[r]) return 0ull;
+    u64 c = 1ull;
+    if (a.kept) { const u64 src = a.kept[r]; c = (u64)fxg_reads_count(a.text, a.ls[2ull * src] + 1u, a.le[2ull * src]); }
+    a.s.cnt[a.rec0 + a.num[r]] = c;
+    return c;
 }
 
 // ---- the table ----
@@ -388,6 +454,8 @@ static inline u64 fxg_cl_grid(u64 items, u64 most) { const u64 g = (items + FXG_
 //   int up(void *dst, const void *src, u64 bytes); int down(void *dst, const void *src, u64 bytes)      both complete when they return
 //   int scan(u64 *data, u64 n, u64 *levels)
 //   int lens(const uint16_t *dlen, u64 n, u64 *tmp); int copy_check(const FxgClAddArgs &); int init(u64 *slots, u64 nslots);
+//   int row_lens(const uint16_t *rlen, u64 n, u32 first, u32 last, u64 *bytes, u64 *num); int copy_rows(const FxgClRowsArgs &);
+//   int row_counts(const FxgClRowsArgs &)                (these three only in a backend that offers fxg_cl_add_rows)
 //   int rebuild(const u64 *old, u64 nold, const FxgClSet &, u32 hash_bits); int insert(const FxgClSet &, u64 rec0, u64 n, u32 hash_bits);
 //   int mark(const FxgClSet &, u64 *flags); int scatter(const FxgClOrd &); int sizes(const FxgClOrd &);
 //   int window(const FxgClOrd &, u64 rank_begin, u64 out_cap); int write(const FxgClOrd &, u64 rank_begin, u64 rank_end); int sync();
@@ -435,6 +503,22 @@ static int fxg_cl_begin(B &b, FxgClState &st, const fxg_collapse_opts *opts)
     return FXG_OK;
 }
 
+// room for n more records' entries
+template <class B>
+static int fxg_cl_grow_records(B &b, FxgClState &st, u64 n)
+{
+    const u64 R = st.records;
+    u64 c1 = st.rec_cap, c2 = st.rec_cap, c3 = st.rec_cap;       // three arrays of one capacity
+    FXG_CL_TRY(fxg_cl_grow(b, &st.off, &c1, R + n, R, sizeof(u64), 0, "its records' offsets"));
+    FXG_CL_TRY(fxg_cl_grow(b, &st.cnt, &c2, c1, R, sizeof(u64), 0, "its records' counts"));
+    FXG_CL_TRY(fxg_cl_grow(b, &st.len, &c3, c1, R, sizeof(uint16_t), 0, "its records' lengths"));
+    st.rec_cap = c1 < c2 ? (c1 < c3 ? c1 : c3) : (c2 < c3 ? c2 : c3);
+    return FXG_OK;
+}
+
+template <class B>
+static int fxg_cl_add_copied(B &b, FxgClState &st, u64 n, u64 bytes, u64 (&res)[FXG_CL_RES_WORDS], fxg_collapse_info *info, const char *who);
+
 template <class B>
 static int fxg_cl_add(B &b, FxgClState &st, const uint8_t *text, u64 text_len, int lpr, const u32 *line, u64 cap_lines, u64 n, const uint16_t *dlen, fxg_collapse_info *info)
 {
@@ -453,13 +537,7 @@ static int fxg_cl_add(B &b, FxgClState &st, const uint8_t *text, u64 text_len, i
     if (n == 0) return FXG_OK;
     // room: the records' entries, the arena (a block's bases are fewer than its bytes), the lengths and their scan
     const u64 R = st.records, M = n + 1;
-    {
-        u64 c1 = st.rec_cap, c2 = st.rec_cap, c3 = st.rec_cap;   // three arrays of one capacity
-        FXG_CL_TRY(fxg_cl_grow(b, &st.off, &c1, R + n, R, sizeof(u64), 0, "its records' offsets"));
-        FXG_CL_TRY(fxg_cl_grow(b, &st.cnt, &c2, c1, R, sizeof(u64), 0, "its records' counts"));
-        FXG_CL_TRY(fxg_cl_grow(b, &st.len, &c3, c1, R, sizeof(uint16_t), 0, "its records' lengths"));
-        st.rec_cap = c1 < c2 ? (c1 < c3 ? c1 : c3) : (c2 < c3 ? c2 : c3);
-    }
+    FXG_CL_TRY(fxg_cl_grow_records(b, st, n));
     FXG_CL_TRY(fxg_cl_grow(b, &st.arena, &st.arena_cap, st.arena_used + text_len, st.arena_used, 1, 64, "its arena"));
     FXG_CL_TRY(fxg_cl_grow(b, &st.tmp, &st.tmp_cap, M + fxg_cl_level_words(M), 0, sizeof(u64), 0, "a block's offsets"));
     u64 res[FXG_CL_RES_WORDS];
@@ -476,6 +554,15 @@ static int fxg_cl_add(B &b, FxgClState &st, const uint8_t *text, u64 text_len, i
     u64 bytes = 0;
     FXG_CL_TRY(b.down(&bytes, st.tmp + n, sizeof bytes));
     FXG_CL_TRY(b.down(res, st.res, sizeof res));
+    return fxg_cl_add_copied(b, st, n, bytes, res, info, "fxg_collapse_add");
+}
+
+// the second half of an add, the same for a block of text and a block of rows: the block's n records lie copied behind the set's end (`bytes`
+// arena bytes, their off / len / cnt entries) and res holds the copy's result words
+template <class B>
+static int fxg_cl_add_copied(B &b, FxgClState &st, u64 n, u64 bytes, u64 (&res)[FXG_CL_RES_WORDS], fxg_collapse_info *info, const char *who)
+{
+    const u64 R = st.records;
     if (res[FXG_CL_RES_IRREGULAR]) {                             // nothing of the block stays: the set ends where it ended before
         info->irregular = FXG_TEXT_IRR_BASE; info->first_bad = res[FXG_CL_RES_FIRST_BAD];
         return FXG_OK;
@@ -485,7 +572,7 @@ static int fxg_cl_add(B &b, FxgClState &st, const uint8_t *text, u64 text_len, i
     if (st.nslots < want) {
         u64 ns = st.nslots;
         while (ns < want) ns *= 2;
-        if (ns > FXG_CL_SLOTS_MAX) FXG_CL_FAIL(b, "fxg_collapse_add: the table would need %llu slots; at most %llu", (unsigned long long)ns, (unsigned long long)FXG_CL_SLOTS_MAX);
+        if (ns > FXG_CL_SLOTS_MAX) FXG_CL_FAIL(b, "%s: the table would need %llu slots; at most %llu", who, (unsigned long long)ns, (unsigned long long)FXG_CL_SLOTS_MAX);
         u64 *fresh = nullptr;
         FXG_CL_TRY(b.alloc((void **)&fresh, ns * 24ull, "a larger table"));
         const u64 *old = st.slots; const u64 nold = st.nslots;
@@ -503,10 +590,59 @@ static int fxg_cl_add(B &b, FxgClState &st, const uint8_t *text, u64 text_len, i
     FXG_CL_TRY(b.insert(fxg_cl_set(st), R, n, st.hash_bits));
     b.interval_end();
     FXG_CL_TRY(b.down(res, st.res, sizeof res));
-    if (res[FXG_CL_RES_ERR]) { st.stage = 0; snprintf(b.err, b.cap, "fxg_collapse_add: a probe ran through all %llu slots (the set is lost)", (unsigned long long)st.nslots); return FXG_E_DEVICE; }
+    if (res[FXG_CL_RES_ERR]) { st.stage = 0; snprintf(b.err, b.cap, "%s: a probe ran through all %llu slots (the set is lost)", who, (unsigned long long)st.nslots); return FXG_E_DEVICE; }
     st.records += n; st.reads += res[FXG_CL_RES_READS]; st.uniques += res[FXG_CL_RES_NEW]; st.arena_used += bytes;
     fxg_cl_info(st, info);
     return FXG_OK;
+}
+
+// fxg_collapse_add_rows: a block of packed rows -- what fxg_run_pipeline leaves in out_bases / out_off / out_len -- into the same set.  first,
+// last: the window of every row that goes in (0 / 1, 0: the whole row).  kept, text, line, cap_lines, lpr: the count source (all or none); it
+// counts for lpr == 2 only.
+template <class B>
+static int fxg_cl_add_rows(B &b, FxgClState &st, const uint8_t *bases, const u64 *roff, const uint16_t *rlen, u64 n, u32 first, u32 last, const u32 *kept,
+                           const uint8_t *text, const u32 *line, u64 cap_lines, int lpr, fxg_collapse_info *info)
+{
+    if (!info) FXG_CL_FAIL(b, "fxg_collapse_add_rows: info is null");
+    memset(info, 0, sizeof *info);
+    info->first_bad = FXG_CL_NONE;
+    if (st.stage == 0) FXG_CL_FAIL(b, "fxg_collapse_add_rows: no set; fxg_collapse_begin makes one");
+    if (st.stage == 2) FXG_CL_FAIL(b, "fxg_collapse_add_rows: the set is ordered and takes no more blocks; fxg_collapse_begin makes another");
+    fxg_cl_info(st, info);
+    const bool source = kept || text || line || cap_lines || lpr;
+    if (source && (!kept || !text || !line || cap_lines < 2))
+        FXG_CL_FAIL(b, "fxg_collapse_add_rows: a count source is d_kept_index, d_text, d_line and cap_lines together, or none of them with lines_per_record 0");
+    if (source && !fxg_text_lpr_ok(lpr)) FXG_CL_FAIL(b, "fxg_collapse_add_rows: lines_per_record %d; 2 (FASTA) or 4 (FASTQ)", lpr);
+    if (last != 0u && last < first) FXG_CL_FAIL(b, "fxg_collapse_add_rows: last_base %u is before first_base %u", last, first);
+    if (n && (!bases || !roff || !rlen)) FXG_CL_FAIL(b, "fxg_collapse_add_rows: a null pointer with %llu records", (unsigned long long)n);
+    if (n > FXG_CL_MAX_RECORDS - st.records) FXG_CL_FAIL(b, "fxg_collapse_add_rows: %llu records after %llu; a set holds at most 2^40 - 2", (unsigned long long)n, (unsigned long long)st.records);
+    if (n == 0) return FXG_OK;
+    const u64 R = st.records, M = n + 1, LV = fxg_cl_level_words(M);
+    FXG_CL_TRY(fxg_cl_grow_records(b, st, n));
+    FXG_CL_TRY(fxg_cl_grow(b, &st.tmp, &st.tmp_cap, 2 * (M + LV), 0, sizeof(u64), 0, "a block's offsets"));
+    u64 *scan = st.tmp, *num = st.tmp + M + LV;
+    u64 res[FXG_CL_RES_WORDS];
+    memset(res, 0, sizeof res);
+    res[FXG_CL_RES_FIRST_BAD] = FXG_CL_NONE;
+    FXG_CL_TRY(b.up(st.res, res, sizeof res));
+    b.interval_begin();
+    FXG_CL_TRY(b.row_lens(rlen, n, first, last, scan, num));
+    FXG_CL_TRY(b.scan(scan, M, scan + M));
+    FXG_CL_TRY(b.scan(num, M, num + M));
+    u64 bytes = 0, m = 0;                                        // the rows' bytes are known only now: the arena's room follows the scan
+    int rc = b.down(&bytes, scan + n, sizeof bytes);
+    if (rc == FXG_OK) rc = b.down(&m, num + n, sizeof m);
+    if (rc == FXG_OK) rc = fxg_cl_grow(b, &st.arena, &st.arena_cap, st.arena_used + bytes, st.arena_used, 1, 64, "its arena");
+    FxgClRowsArgs a;
+    a.bases = bases; a.roff = roff; a.rlen = rlen; a.first = first; a.last = last; a.kept = source && lpr == 2 ? kept : nullptr; a.text = text; a.ls = line;
+    a.le = line + cap_lines; a.n = n; a.scan = scan; a.num = num; a.rec0 = R; a.off0 = st.arena_used; a.s = fxg_cl_set(st);
+    if (rc == FXG_OK) rc = b.copy_rows(a);
+    if (rc == FXG_OK) rc = b.row_counts(a);
+    b.interval_end();
+    FXG_CL_TRY(rc);
+    FXG_CL_TRY(b.down(res, st.res, sizeof res));
+    if (m == 0 && !res[FXG_CL_RES_IRREGULAR]) return FXG_OK;     // every row ends before the window: nothing to insert
+    return fxg_cl_add_copied(b, st, m, bytes, res, info, "fxg_collapse_add_rows");
 }
 
 template <class B>
@@ -609,6 +745,48 @@ __global__ __launch_bounds__(FXG_BLOCK) void fxg_kernel_cl_copy(const FxgClAddAr
         }
         if (fxg_lane() == 0) { fxg_cl_a_min(a.s.res + FXG_CL_RES_FIRST_BAD, first); fxg_cl_a_or(a.s.res + FXG_CL_RES_IRREGULAR, 1ull); }
     }
+}
+
+// the irregular word and the smallest irregular record of a wave, as fxg_kernel_cl_copy raises them
+__device__ __forceinline__ void fxg_cl_raise_first(u64 *res, u64 first)
+{
+    if (__ballot(first != FXG_CL_NONE) == 0ull) return;          // (wave-uniform, and rare: the host drops the block)
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) {
+        const u64 o = ((u64)__shfl_xor((u32)(first >> 32), d, 64) << 32) | __shfl_xor((u32)first, d, 64);
+        first = o < first ? o : first;
+    }
+    if (fxg_lane() == 0) { fxg_cl_a_min(res + FXG_CL_RES_FIRST_BAD, first); fxg_cl_a_or(res + FXG_CL_RES_IRREGULAR, 1ull); }
+}
+
+__global__ __launch_bounds__(FXG_BLOCK) void fxg_kernel_cl_row_lens(const uint16_t *rlen, u64 n, u32 first, u32 last, u64 *bytes, u64 *num)
+{
+    const u64 r = (u64)blockIdx.x * FXG_BLOCK + threadIdx.x;
+    if (r <= n) fxg_cl_row_len(rlen, n, first, last, r, bytes, num);
+}
+
+// 16 lanes to a row, at most FXG_CL_GRID_MAX workgroups with further trips, as fxg_kernel_cl_copy
+__global__ __launch_bounds__(FXG_BLOCK) void fxg_kernel_cl_copy_rows(const FxgClRowsArgs a)
+{
+    const u64 g0 = ((u64)blockIdx.x * FXG_BLOCK + threadIdx.x) / FXG_CL_LANES, groups = (u64)gridDim.x * (FXG_BLOCK / FXG_CL_LANES);
+    const u32 l = threadIdx.x & (FXG_CL_LANES - 1u);
+    u64 first = FXG_CL_NONE;
+    for (u64 r = g0; r < a.n; r += groups)
+        if (fxg_cl_copy_row(a, r, l) && first == FXG_CL_NONE) first = r;      // (r only grows)
+    fxg_cl_raise_first(a.s.res, first);
+}
+
+// a lane to a row, further trips as above
+__global__ __launch_bounds__(FXG_BLOCK) void fxg_kernel_cl_row_counts(const FxgClRowsArgs a)
+{
+    u64 reads = 0;
+    for (u64 r = (u64)blockIdx.x * FXG_BLOCK + threadIdx.x; r < a.n; r += (u64)gridDim.x * FXG_BLOCK) reads += fxg_cl_row_count(a, r);
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) {
+        const u32 lo = __shfl_down((u32)reads, d, 64), hi = __shfl_down((u32)(reads >> 32), d, 64);
+        reads += ((u64)hi << 32) | lo;
+    }
+    if (fxg_lane() == 0 && reads) fxg_cl_a_add(a.s.res + FXG_CL_RES_READS, reads);
 }
 
 __global__ __launch_bounds__(FXG_BLOCK) void fxg_kernel_cl_init(u64 *slots, u64 nslots)

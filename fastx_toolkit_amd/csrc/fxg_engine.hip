@@ -832,6 +832,8 @@ int fxg_collapse_write(fxg_ctx *c, uint64_t rank_begin, uint64_t out_cap, uint8_
     return fxg_cl_write(b, *fxg_cl_state(c, &none), rank_begin, out_cap, d_out, window);
 }
 
+#include "fxg_collapse_rows_engine.h"      // fxg_collapse_add_rows: its launches and its entry
+
 extern "C" int fxg_host_register(fxg_ctx *c, void *ptr, size_t bytes)
 {
     if (!c || !ptr) return FXG_E_INVALID;

@@ -27,7 +27,7 @@ EXPORTS = [
     "fxg_fastq_index", "fxg_fastq_pack", "fxg_fastq_format", "fxg_fastq_format_opts", "fxg_fasta_weights", "fxg_host_register", "fxg_host_unregister",
     "fxg_shard_range", "fxg_epilogue", "fxg_concat_pwrite", "fxg_concat_peer", "fxg_device_count", "fxg_device_numa_node", "fxg_comm_create", "fxg_comm_destroy", "fxg_epilogue_rccl",
     "fxg_barcode_prepare", "fxg_barcode_split", "fxg_fasta_reflow", "fxg_fasta_uncollapse", "fxg_bases_change",
-    "fxg_collapse_begin", "fxg_collapse_add", "fxg_collapse_order", "fxg_collapse_write",
+    "fxg_collapse_begin", "fxg_collapse_add", "fxg_collapse_order", "fxg_collapse_write", "fxg_collapse_add_rows",
 ]
 
 
@@ -222,6 +222,8 @@ def load_library(path=None):
         L.fxg_collapse_add.argtypes = [vp, vp, u64, i32, vp, u64, u64, vp, C.POINTER(FxgCollapseInfo)]
         L.fxg_collapse_order.argtypes = [vp, C.POINTER(FxgCollapseInfo)]
         L.fxg_collapse_write.argtypes = [vp, u64, u64, vp, C.POINTER(FxgCollapseWindow)]
+    if hasattr(L, "fxg_collapse_add_rows"):  # (as above)
+        L.fxg_collapse_add_rows.argtypes = [vp, vp, vp, vp, u64, u32, u32, vp, vp, vp, u64, i32, C.POINTER(FxgCollapseInfo)]
     L.fxg_set_profiling.argtypes = [vp, i32]
     L.fxg_set_clip_history.argtypes = [vp, i32]
     L.fxg_run_quality_stats.argtypes = [vp, C.POINTER(FxgBatch), vp, C.c_uint32]
@@ -642,6 +644,35 @@ class Engine:
         self._after_torch()
         self._check(self.lib.fxg_collapse_add(self.ctx, d_text.data_ptr() if d_text is not None else None, text_len, ix.lpr, ix.line.data_ptr(), ix.cap_lines, n,
                                               lens.data_ptr() if lens is not None else None, C.byref(info)))
+        return info
+
+    def collapse_add_rows(self, rows, n=None, d_text=None, ix=None, first_base=1, last_base=0):
+        """One block of packed rows into the set without leaving the device (fxg_collapse_add_rows in include/fxg.h).  rows: a Result of run()
+        with compacted outputs (its out_bases / out_off / out_len, n defaulting to its kept count), or a tuple (bases, off, lens[, kept_index])
+        of device tensors with n given.  d_text and ix (text_upload, fastq_index): the block the rows were packed from, the count source --
+        with FASTA text record k counts what the id of source record kept_index[k] says; without them every record counts 1.  first_base /
+        last_base: the window of every row that goes in, as fastx_trimmer -f / -l (a row that ends before first_base is left out).  Returns
+        the info, as collapse_add."""
+        if not hasattr(self.lib, "fxg_collapse_add_rows"):
+            raise FxgError("this libfxg.so has no fxg_collapse_add_rows")
+        if isinstance(rows, Result):
+            bases, off, lens, kept = rows.out_bases, rows.out_off, rows.out_len, rows.kept_index
+            n = rows.kept if n is None else n
+        else:
+            bases, off, lens = rows[:3]
+            kept = rows[3] if len(rows) > 3 else None
+        if n is None:
+            raise FxgError("collapse_add_rows: n is needed with plain tensors")
+        if (d_text is None) != (ix is None) or (ix is not None and kept is None):
+            raise FxgError("collapse_add_rows: the count source is d_text, ix and the rows' kept_index together")
+        ptr = lambda t: t.data_ptr() if t is not None else None
+        info = FxgCollapseInfo()
+        self._after_torch()
+        if ix is None:
+            rc = self.lib.fxg_collapse_add_rows(self.ctx, ptr(bases), ptr(off), ptr(lens), n, first_base, last_base, None, None, None, 0, 0, C.byref(info))
+        else:
+            rc = self.lib.fxg_collapse_add_rows(self.ctx, ptr(bases), ptr(off), ptr(lens), n, first_base, last_base, ptr(kept), ptr(d_text), ix.line.data_ptr(), ix.cap_lines, ix.lpr, C.byref(info))
+        self._check(rc)
         return info
 
     def collapse_order(self):

@@ -193,6 +193,10 @@ typedef struct fxg_out {
  *   bases change (below)     d_text: read as for the text path (text_len + 16 bytes), written only inside the records' bases lines, from a
  *                            line's start to its chomped end; d_line: 2 * cap_lines uint32, read at entries lines_per_record * r + 1 of
  *                            either half.
+ *   collapse rows (below)    d_bases: read only inside [d_off[k], d_off[k] + d_len[k]) of records k = 0 .. records - 1, rounded out to 16-byte
+ *                            granules, and never past the granule that holds the last record's last byte; d_off, d_len, d_kept_index: read at
+ *                            entries 0 .. records - 1; d_text: the id lines of the records d_kept_index names; d_line: 2 * cap_lines uint32,
+ *                            read at entries 2 * d_kept_index[k] of either half.
  * tests/test_emu_bounds.py runs the kernels' bodies with every array against a guard page at these ends; tests/test_gpu_bounds.py surrounds every
  * array with poison (inputs) and canaries (outputs) on the device. */
 
@@ -447,6 +451,20 @@ int  fxg_bases_change(fxg_ctx *ctx, uint8_t *d_text, uint64_t text_len, int line
  *                        block irregular: info->irregular = FXG_TEXT_IRR_BASE, info->first_bad the smallest such record of the block, and
  *                        NOTHING of the block stays in the set -- the call returns FXG_OK and the set is what it was.  Blocks are added in
  *                        input order: the order of equal counts in the output depends on it.  Synchronises.
+ *   fxg_collapse_add_rows  one block of packed rows into the same set, arena and record numbering, without leaving the device: record k is
+ *                        d_len[k] bytes at d_bases + d_off[k] (no alignment), which is what fxg_run_pipeline leaves in out_bases / out_off /
+ *                        out_len for kept read k, with records = counters[FXG_C_KEPT].  The rows came from a pack that checked the alphabet,
+ *                        so it is not checked again.  The count source is optional: d_kept_index (fxg_out.kept_index) with the d_text, d_line,
+ *                        cap_lines and lines_per_record of the indexed block the rows were packed from.  With lines_per_record == 2 record k
+ *                        counts what the id line of source record d_kept_index[k] says, as above; with 4, or without a count source (all
+ *                        five arguments null / 0), every record counts 1.  A d_len entry of zero makes the block irregular exactly as an
+ *                        empty bases line does: FXG_TEXT_IRR_BASE, first_bad the smallest such k, nothing of the block in the set, FXG_OK.
+ *                        first_base / last_base (0 or 1, 0: the whole row) cut every row as fastx_trimmer -f / -l does before it goes in:
+ *                        bases first_base .. min(last_base, d_len[k]) counted from 1; a row that ends before first_base is left out as the
+ *                        trimmer leaves it out -- it gets no record number, and info->records / ->reads tell how many went in.  (The engine
+ *                        runs no chain of CLIP and FTRIM in one launch; this is how clip | trim | collapse stays on the device.)
+ *                        Blocks of text and blocks of rows may alternate within one set; everything after the copy -- the table, the
+ *                        rebuild rule, order and write -- is the same code.  Synchronises.
  *   fxg_collapse_order   after the last block: numbers the distinct sequences in first-occurrence order, downloads 16 bytes per distinct
  *                        sequence (hash and count), replays the reference's container on the host -- a std::unordered_map filled in that
  *                        order, iterated, stable-sorted by count, read backwards -- and sizes the output.  The result is byte-identical to the
@@ -460,15 +478,17 @@ int  fxg_bases_change(fxg_ctx *ctx, uint8_t *d_text, uint64_t text_len, int line
  *                        never a byte past them.  rank_begin == uniques is a valid call that writes nothing.  Synchronises.
  * Refused (FXG_E_INVALID with a message, nothing launched, d_out untouched): add, order or write before begin; add or order after order; write
  * before order; more than 2^40 - 2 records in a set; a null pointer with records > 0; lines_per_record other than 2 or 4; more records than
- * cap_lines or text_len can hold, text_len above 0xFFFFFFF0; rank_begin above uniques; an out_cap smaller than record rank_begin (the message
+ * cap_lines or text_len can hold, text_len above 0xFFFFFFF0; add_rows with only some of the count source's arguments, or with a count source and
+ * lines_per_record other than 2 or 4, or with a last_base before first_base; rank_begin above uniques; an out_cap smaller than record rank_begin (the message
  * says how many bytes it needs).  A device allocation that fails is FXG_E_NOMEM and says how many bytes the set wanted; the set is then as it
  * was before the call.  What a refused call leaves in its results: add and order refused for the set's state (no set, or an ordered one) leave
  * *info zeroed with first_bad = ~0ull; add refused for its arguments leaves the set's counts as they are (records, reads, uniques, slots,
- * rebuilds), irregular = 0 and first_bad = ~0ull; a refused write leaves *window zeroed with rank_end = rank_begin.
+ * rebuilds), irregular = 0 and first_bad = ~0ull (add_rows as add in both); a refused write leaves *window zeroed with rank_end = rank_begin.
  * The set is resident: its device memory is about the bases + 18 bytes per record + 48 to 96 bytes per distinct sequence (a table that is at
  * most half full), and fxg_collapse_order needs 8 more per record and 40 per distinct sequence while it runs; the host replay takes about 48
  * bytes per distinct sequence.  With profiling on, add records an interval for lengths + scan + copy + check, one for a rebuild of the table
- * if the block caused one, and one for the insert; order records two (mark + scan + scatter; sizes + scan), write one. */
+ * if the block caused one, and one for the insert; add_rows records the same three (its first: lengths + scan + copy rows + counts, and the
+ * download of the block's byte count between the scan and the copy, which sizes the arena); order records two (mark + scan + scatter; sizes + scan), write one. */
 typedef struct fxg_collapse_opts {
     /* Both fields are test and measurement aids: they never change a result.  A null opts is {0, 0}. */
     uint64_t initial_slots;  /* slots of the table at first, rounded up to a power of two, 4 at the least; 0: the default, 65 536.  The table
@@ -494,6 +514,9 @@ typedef struct fxg_collapse_window {
 int  fxg_collapse_begin(fxg_ctx *ctx, const fxg_collapse_opts *opts);
 int  fxg_collapse_add(fxg_ctx *ctx, const uint8_t *d_text, uint64_t text_len, int lines_per_record, const uint32_t *d_line, uint64_t cap_lines,
                       uint64_t records, const uint16_t *d_len, fxg_collapse_info *info);
+int  fxg_collapse_add_rows(fxg_ctx *ctx, const uint8_t *d_bases, const uint64_t *d_off, const uint16_t *d_len, uint64_t records,
+                           uint32_t first_base, uint32_t last_base, const uint32_t *d_kept_index, const uint8_t *d_text, const uint32_t *d_line, uint64_t cap_lines, int lines_per_record,
+                           fxg_collapse_info *info);
 int  fxg_collapse_order(fxg_ctx *ctx, fxg_collapse_info *info);
 int  fxg_collapse_write(fxg_ctx *ctx, uint64_t rank_begin, uint64_t out_cap, uint8_t *d_out, fxg_collapse_window *window);
 int  fxg_host_register(fxg_ctx *ctx, void *ptr, size_t bytes);     /* page-lock an existing host buffer for async copies */
