@@ -547,12 +547,17 @@ __device__ __forceinline__ void fxg_wait_prefix_wave(const FxgKArgs &a, u32 tile
     u64 v = fxg_peek_prefix(a, tile);
     u32 spins = 0;
     const u64 t0 = __builtin_amdgcn_s_memrealtime();
-    while (__ballot((u32)(v >> FXG_TAG_SHIFT) != a.tag) != 0ull) {
+    // The tag is compared right behind every load, on every path out of the loop.  With the comparison at the loop's head the generated code had a
+    // (never taken) exit on which the granule's registers still counted as outstanding, and the compiler then put s_waitcnt vmcnt(0) in front of
+    // their next writes, far into the caller: between the rows kernels' next-ticket atomic and the quality flush, and in front of the base fetch
+    // (profiles/rows_pack/isa_waits.md).
+    bool ok = __ballot((u32)(v >> FXG_TAG_SHIFT) != a.tag) == 0ull;
+    while (!ok) {
         __builtin_amdgcn_s_sleep(FXG_POLL_SLEEP);
         if (lane < 2u) v = fxg_granule_load(a.pfx + 2 * (u64)tile + lane);
-        if ((++spins & 255u) == 0u && fxg_spin_expired(a, t0)) break;
+        ok = __ballot((u32)(v >> FXG_TAG_SHIFT) != a.tag) == 0ull;
+        if (!ok && (++spins & 255u) == 0u && fxg_spin_expired(a, t0)) break;  // expired: a stale granule of an earlier launch, see fxg_wait_prefix
     }
-    const bool ok = __ballot((u32)(v >> FXG_TAG_SHIFT) != a.tag) == 0ull;      // expired: a stale granule of an earlier launch, see fxg_wait_prefix
     v = ok ? FXG_TAG_VALUE(v) : ~0ull;                      // scalars from here on
     bc[0] = ((u64)(u32)__builtin_amdgcn_readlane((int)(v >> 32), 0) << 32) | (u32)__builtin_amdgcn_readlane((int)(u32)v, 0);
     bc[1] = ((u64)(u32)__builtin_amdgcn_readlane((int)(v >> 32), 1) << 32) | (u32)__builtin_amdgcn_readlane((int)(u32)v, 1);

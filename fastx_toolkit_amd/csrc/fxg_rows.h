@@ -205,6 +205,37 @@ FXG_HD u32 fxg_rows_need_mask(u32 lane, u32 stride, u32 magic, u32 tbytes, PERM 
     return m;
 }
 
+// ---- the unpredicated (`fast`) pack of a kept prefix, as a write schedule (fxg_rows_pack) ----
+// A lane puts the first `len` bytes of row[] into the staging buffer at byte D, the read's place in the tile's packed output.  `fast` is
+// wave-uniform: every kept read of the tile has at least 4 bytes.  Every lane then writes ALL its dwords, from the top down and without
+// predicates, in NW + 3 steps; step S is ONE LDS store instruction of the wave (two where the lanes differ in width), and a wave's LDS
+// instructions execute in issue order:
+//   S < NW       dword j = NW - S of the output, at byte (D & ~3) + 4 j: row bytes 4 j - al ... 4 j - al + 3, al = D & 3 (v_perm_b32)
+//   S = NW       al = 0: dword 0 = row[0];  else the first head byte, at D
+//   S = NW + 1   al = 1, 2: the second head byte;   S = NW + 2   al = 1: the third
+// What a lane writes past its own bytes lands in dwords that start inside a later read, and that read's lane writes them in a LATER
+// step (its index for the same address is smaller), so the right bytes win; the dword a read shares with its predecessor only gets the
+// read's own head bytes, last of all.  Nothing depends on the order of the lanes inside one step: kept reads of 4 bytes and more start in
+// different dwords, so no two lanes write the same dword in a dword step, and the head steps write a read's own bytes only
+// (tests/emu/rows_pack.cpp runs this schedule with the lanes of every step shuffled).
+struct FxgPackStore { u32 base, width, value; };      // the lane stores `width` (4, 1, or 0: nothing) bytes of `value` at base + fxg_rows_pack_off<NW, S>()
+#define FXG_ROWS_PACK_STEPS(NW) ((NW) + 3)
+template <int NW, int S>
+constexpr u32 fxg_rows_pack_off() { return S < NW ? 4u * (u32)(NW - S) : (u32)(S - NW); }   // the instruction's offset field: the same for every lane
+template <int NW, int S>
+FXG_HD FxgPackStore fxg_rows_pack_step(u32 D, const u32 (&row)[NW])
+{
+    static_assert(S >= 0 && S < FXG_ROWS_PACK_STEPS(NW), "NW dword steps and three head steps");
+    const u32 al = D & 3u;
+    if constexpr (S < NW) {
+        constexpr int j = NW - S;
+        const u32 sel = 0x07060504u - al * 0x01010101u;
+        return {D & ~3u, 4u, fxg_perm(j < NW ? row[j < NW ? j : 0] : 0u, row[j - 1], sel)};
+    } else if constexpr (S == NW) return {D, al == 0u ? 4u : 1u, row[0]};
+    else if constexpr (S == NW + 1) return {D, al == 1u || al == 2u ? 1u : 0u, row[0] >> 8};
+    else return {D, al == 1u ? 1u : 0u, row[0] >> 16};
+}
+
 #ifndef FXG_HOST_EMULATION
 // A workgroup is ONE wave: its LDS accesses execute in order, so "every lane's reads / writes before this point are done" needs no
 // barrier, only the wave's own LDS counter at zero and the compiler kept from moving accesses across the point.
@@ -283,28 +314,34 @@ __device__ __forceinline__ void fxg_rows_read(const unsigned char *sbuf, u32 bas
     }
 }
 
-// The lane's first `len` bytes of row[] into the staging buffer at byte D (the read's place in the tile's packed output):
-// up to three head bytes to reach a dword boundary, dwords of the row shifted to match, up to three tail bytes.
-// `fast` (wave-uniform: every kept read of the tile has at least 4 bytes): every lane writes ALL its dwords, from the top down and
-// without predicates.  What a lane writes past its own bytes lands in dwords that start inside a later read, and that read's lane
-// writes them in a LATER step (its index for the same address is smaller), so the right bytes win; the dword a read shares with
-// its predecessor only gets the read's own head bytes, last of all.
+// One step of the fast pack's schedule (fxg_rows_pack_step) as explicit LDS store instructions: ds_write_b32 / ds_write_b8 on the lane's
+// LDS byte address, the step's offset in the instruction.  Written out because the order IS the correctness argument and the stores must
+// issue back to back: through a volatile generic pointer the compiler emitted a flat store per dword, each followed by s_waitcnt vmcnt(0)
+// -- 42 round trips through the vector-memory path per pack (profiles/rows_pack/isa_waits.md).  No wait here -- but the compiler does not see
+// inside the asm and counts no lgkmcnt for these stores: every call of fxg_rows_pack MUST be followed by FXG_WAVE_SYNC() (its explicit
+// s_waitcnt lgkmcnt(0)) before anything reads the buffer; the compiler-generated LDS reads of fxg_rows_flush rely on it.
+template <int NW, int S>
+__device__ __forceinline__ void fxg_rows_pack_emit(u32 lds0, u32 D, const u32 (&row)[NW])
+{
+    if constexpr (S < FXG_ROWS_PACK_STEPS(NW)) {
+        const FxgPackStore st = fxg_rows_pack_step<NW, S>(D, row);
+        const u32 addr = lds0 + st.base;
+        if (S < NW || st.width == 4u) asm volatile("ds_write_b32 %0, %1 offset:%2" :: "v"(addr), "v"(st.value), "n"(fxg_rows_pack_off<NW, S>()) : "memory");
+        else if (st.width == 1u) asm volatile("ds_write_b8 %0, %1 offset:%2" :: "v"(addr), "v"(st.value), "n"(fxg_rows_pack_off<NW, S>()) : "memory");
+        fxg_rows_pack_emit<NW, S + 1>(lds0, D, row);
+    }
+}
+
+// The lane's first `len` bytes of row[] into the staging buffer at byte D (the read's place in the tile's packed output).
+// `fast`: the schedule of fxg_rows_pack_step, one LDS store instruction per step.  Otherwise, predicated: up to three head bytes to reach a
+// dword boundary, dwords of the row shifted to match, up to three tail bytes.
+// The caller follows every pack (or run of packs) with FXG_WAVE_SYNC() before the buffer is read: the fast path's stores are inline asm,
+// which the compiler's wait-count pass does not track (fxg_rows_pack_emit).
 template <int NW>
 __device__ __forceinline__ void fxg_rows_pack(unsigned char *obuf, u32 D, const u32 (&row)[NW], u32 len, bool fast)
 {
     if (fast) {
-        const u32 al = D & 3u;
-        const u32 sel = 0x07060504u - al * 0x01010101u;          // v_perm_b32: dword j of the output = row bytes 4 j - al ... 4 j - al + 3
-        volatile u32 *w = reinterpret_cast<volatile u32 *>(obuf + (D & ~3u));   // volatile: this order, one dword per instruction
-#pragma unroll
-        for (int j = NW; j >= 1; --j) w[j] = __builtin_amdgcn_perm(j < NW ? row[j] : 0u, row[j - 1], sel);
-        volatile unsigned char *p = obuf + D;
-        if (al == 0u) w[0] = row[0];
-        else {
-            p[0] = (unsigned char)row[0];
-            if (al <= 2u) p[1] = (unsigned char)(row[0] >> 8);
-            if (al == 1u) p[2] = (unsigned char)(row[0] >> 16);
-        }
+        fxg_rows_pack_emit<NW, 0>((u32)(uintptr_t)(fxg_lds_u8 *)obuf, D, row);
         return;
     }
     u32 h = (0u - D) & 3u;
@@ -360,6 +397,18 @@ __device__ __forceinline__ void fxg_rows_flush(uint8_t *out, u64 base, u32 totb,
     const u32 ts = whole ? (end << 4) - sh : totb;
     if (lane < hb) out[base + lane] = obuf[lane];
     if (ts + lane < totb) out[base + ts + lane] = obuf[ts + lane];
+}
+
+// The next tile's ticket, drawn by ONE lane (the caller's `if (lane == 0)`) and not waited for here.  The counter's address is made opaque
+// to the compiler: for a wave-uniform address its atomic optimiser rewrites the add as mbcnt / readfirstlane and waits for the return on
+// the spot (s_waitcnt vmcnt(0) right behind global_atomic_add: a device-scope round trip per tile with nothing else in flight).  As it is,
+// the same instruction returns into the lane's register and the wait stands at the value's first use, the loop's end.
+__device__ __forceinline__ u32 fxg_rows_draw_ticket(u32 *ticket)
+{
+    typedef __attribute__((address_space(1))) u32 glb_u32;                   // a global address by type: the opaque pointer would otherwise be a flat one
+    glb_u32 *t = (glb_u32 *)ticket;
+    asm volatile("" : "+v"(t));
+    return __hip_atomic_fetch_add(t, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // = atomicAdd
 }
 
 #ifdef FXG_ABLATION
@@ -469,7 +518,7 @@ __global__ __launch_bounds__(64, FXG_ROWS_LB) void fxg_kernel_rows(const FxgKArg
             FXG_PHASE(2);
         }
         u32 nxt = 0;
-        if (havec && lane == 0) nxt = atomicAdd(my_ticket, 1u);               // next ticket: in flight during the write-out (never held across a wait)
+        if (havec && lane == 0) nxt = fxg_rows_draw_ticket(my_ticket);        // next ticket: in flight during the write-out (never held across a prefix wait), read at the loop's end
         if (havep) {
             const u32 r0 = pend * TR;
             const u64 left = a.n - (u64)r0;
@@ -484,27 +533,32 @@ __global__ __launch_bounds__(64, FXG_ROWS_LB) void fxg_kernel_rows(const FxgKArg
             if (keep && !FXG_DBG(a, 64u)) fxg_rows_pack<NW>(smem, exb, qp, olen, fast);
             FXG_WAVE_SYNC();
             FXG_PHASE(6);
-            if (placed && !FXG_DBG(a, 1u)) fxg_rows_flush(a.out_qual, bc[1], p_totb, smem, lane);
-            if constexpr (H == 1) { if (keep) fxg_write_kept_meta(a, bc[0] + p_exc, olen, r0 + lane, bc[1] + exb); }
-            else {                                                            // the first piece speaks for the read (it is never empty when the read is kept)
-                const u32 oo = (u32)__builtin_amdgcn_mov_dpp((int)olen, 0xB1, 0xf, 0xf, true);
-                if (keep && hf == 0u) fxg_write_kept_meta(a, bc[0] + p_exc, olen + oo, r0 + rd, bc[1] + exb);
-            }
-            FXG_WAVE_SYNC();                                                  // the buffer is free again
-            FXG_PHASE(3);
-            // the base rows take the same road: HBM -> staging buffer -> registers -> packed -> out -- only the chunks that hold kept
-            // prefixes (FXG_ROWS_SPARSE_BASES), nothing at all for a tile that keeps no byte or was not placed
-            if (!FXG_DBG(a, 4u) && (!FXG_ROWS_SPARSE_BASES || (placed && p_totb != 0u))) {
-                u32 b[NW];
-                u32 need = ~0u;
+            // the base rows are fetched only in the chunks that hold kept prefixes (FXG_ROWS_SPARSE_BASES), not at all for a tile that keeps no byte or was
+            // not placed.  The mask is made here, ahead of the quality flush, so that the fetch can go out the moment the flush has read the buffer.
+            const bool fetchb = !FXG_DBG(a, 4u) && (!FXG_ROWS_SPARSE_BASES || (placed && p_totb != 0u));
+            u32 need = ~0u;
 #if FXG_ROWS_SPARSE_BASES
+            if (fetchb) {
                 u32 kw = keep ? olen : 0u;                                    // klen word: H = 1, the lane's own read
                 if constexpr (H == 2) {                                       // lane 2r: the read's kept length, both pieces
                     const u32 oo = (u32)__builtin_amdgcn_mov_dpp((int)olen, 0xB1, 0xf, 0xf, true);
                     kw = keep && hf == 0u ? olen + oo : 0u;
                 }
                 need = fxg_rows_base_need<NW, H, 1>(kw, lane, stride, magic, tbytes);
+            }
 #endif
+            if (placed && !FXG_DBG(a, 1u)) fxg_rows_flush(a.out_qual, bc[1], p_totb, smem, lane);
+            if constexpr (H == 1) { if (keep) fxg_write_kept_meta(a, bc[0] + p_exc, olen, r0 + lane, bc[1] + exb); }
+            else {                                                            // the first piece speaks for the read (it is never empty when the read is kept)
+                const u32 oo = (u32)__builtin_amdgcn_mov_dpp((int)olen, 0xB1, 0xf, 0xf, true);
+                if (keep && hf == 0u) fxg_write_kept_meta(a, bc[0] + p_exc, olen + oo, r0 + rd, bc[1] + exb);
+            }
+            FXG_WAVE_SYNC();                                                  // the flush has read the buffer (its stores are NOT waited for): free again
+            FXG_PHASE(3);
+            // the base rows take the same road: HBM -> staging buffer -> registers -> packed -> out; fxg_rows_landed() waits for the quality flush's
+            // stores and this fetch together
+            if (fetchb) {
+                u32 b[NW];
                 fxg_rows_fetch<NW, FXG_ROWS_SPARSE_BASES != 0>(a.bases, tb, tbytes, lsm, lane, need);
                 fxg_rows_landed();
                 FXG_PHASE(4);
@@ -542,7 +596,8 @@ __global__ __launch_bounds__(64, FXG_ROWS_LB) void fxg_kernel_rows(const FxgKArg
 // tile: what a 64-read tile of 150-byte rows is), fetched by ONE LDS-DMA burst, published as ONE total, placed by ONE prefix and flushed once per array; lane l
 // holds reads l, l + 64, ... of the tile, so that sub-tile j is a contiguous run of the packed output and the sub-tiles are packed in order: what the
 // unpredicated pack of one sub-tile writes past its own bytes lands in bytes of a LATER sub-tile (or the buffer's slack) and is overwritten by it, exactly as
-// between the lanes of one sub-tile (fxg_rows_pack).  Everything else is fxg_kernel_rows<NW, 1>: same decisions (fxg_rows_decide), same scanners, same flush.
+// between the lanes of one sub-tile (fxg_rows_pack).  Everything else is fxg_kernel_rows<NW, 1>: same decisions (fxg_rows_decide), same scanners, same flush --
+// except that stage B here still makes the need mask behind the quality flush (it exists only with FXG_ROWS_SPARSE_BASES=2, off by default).
 // ------------------------------------------------------------------------------------------------
 template <int NW, int R>
 __global__ __launch_bounds__(64, FXG_ROWS_LB) void fxg_kernel_rows_multi(const FxgKArgs a)
@@ -613,7 +668,7 @@ __global__ __launch_bounds__(64, FXG_ROWS_LB) void fxg_kernel_rows_multi(const F
         u64 bc[2] = {0, 0};
         if (havep) fxg_wait_prefix_wave(a, pend, bc);
         u32 nxt = 0;
-        if (havec && lane == 0) nxt = atomicAdd(my_ticket, 1u);
+        if (havec && lane == 0) nxt = fxg_rows_draw_ticket(my_ticket);
         if (havep) {
             const u32 r0 = pend * TR;
             const u64 left = a.n - (u64)r0;
